@@ -12,7 +12,14 @@ path over the rank's 16 GiB shard, inputs already resident in HBM:
 value = input bytes of all ranks / max-over-ranks step time (weak scaling).
 The round trip is verified bit-exact on the device after the timed loop.
 
+A plain run sets up, warms up, times the K steps, checks the round trip and prints
+the headline line. --full adds everything else the benchmark measures: the drop-in
+(index-less) path timed the same way, serialised per-kernel times and rooflines,
+the index rebuild, the N > 1 reassembly and the CPU baseline. --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs below).
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--dist zipf|uniform]
+                       [--full] [--dump-outputs DIR]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 import argparse
@@ -42,6 +49,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=16 << 30, help="input bytes per GPU")
     ap.add_argument("--dist", default="zipf", choices=["zipf", "uniform"])
+    ap.add_argument("--full", action="store_true",
+                    help="also: the drop-in path timed like the headline, per-kernel times and rooflines, the index "
+                         "rebuild, the N>1 reassembly, the CPU baseline (the options below apply to these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-sample-mib", type=int, default=128, help="one-process CPU baseline sample")
     ap.add_argument("--cpu-par-sample-mib", type=int, default=48, help="per-process sample, all-core CPU baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -49,7 +61,36 @@ def parse():
     ap.add_argument("--no-reassemble", action="store_true", help="N>1: skip the (untimed-in-step) stream reassembly")
     ap.add_argument("--rehearse", action="store_true",
                     help="N>1 rehearsal on one GPU: every rank on cuda:0, gloo collectives through host copies")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22  # bytes kept of a longer output (float32: 16 MiB a file, 3 such files at most)
+DUMP_SEED = 42
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: {name: array} -> DIR/<name>.npy. Byte arrays (device tensors or host bytes) are
+    written as float32, counts as float64 (both exact). An array longer than DUMP_SAMPLE is written as
+    a fixed sample of DUMP_SAMPLE of its elements: positions drawn from a host generator seeded with
+    DUMP_SEED and sorted, the same for every run and every build at the same length. A Huffman payload
+    that differs anywhere differs in length or in most bytes after, so a sample shows it."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        if isinstance(t, bytes):
+            t = torch.frombuffer(bytearray(t), dtype=torch.uint8) if t else torch.empty(0, dtype=torch.uint8)
+        wide = t.dtype == torch.int64
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            g = torch.Generator()
+            g.manual_seed(DUMP_SEED)
+            pos = torch.randint(0, n, (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+            t = t[pos.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float64 if wide else np.float32))
 
 
 def _cpu_info():
@@ -426,7 +467,7 @@ def main():
         return time.perf_counter() - t0
 
     endb = torch.zeros(2, dtype=torch.int64, device=dev)
-    if world > 1:
+    if world > 1 and args.full:  # the drop-in path's split decode
         split["summ"] = torch.zeros(4, dtype=torch.int64, device=dev)
         split["cap"] = nsym + 32 * HALO  # a part's symbols: its shard's give or take the halo's bits
         split["out"] = torch.empty(2 * split["cap"] + 16, dtype=torch.uint8, device=dev)
@@ -439,6 +480,78 @@ def main():
     elapsed = timed(args.steps)
     codec.sync()  # surfaces device-side errors (capacity, format)
     ok = bool(torch.equal(out[:2 * nsym], x[:2 * nsym]))
+
+    def headline(ms_step, plan, ok):
+        """The result line every run prints: the timed steps' figure and what it was measured on."""
+        C = plan.payload_bits // 8
+        return {
+            "metric": "encode + decode throughput GB/s and % HBM3E peak, 16 GiB Zipf(1.1), 1/2/4/8 GPU",
+            "value": round(n_total / (ms_step / 1e3) / 1e9, 2),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": f"synthetic {args.dist} byte stream (splitmix64 seed 42, counter-based; rank g = bytes "
+                    f"[g*N,(g+1)*N) of one stream), generated in HBM",
+            "config": {
+                "workload": f"{N / 2**30:g} GiB {'Zipf(1.1)' if kind else 'uniform'} bytes per GPU: "
+                            "hist16 -> codebook -> pack -> decode, one global bit stream",
+                "bytes_per_gpu": N,
+                "total_bytes": n_total,
+                "symbols_per_gpu": nsym,
+                "parallelism": f"shard{world}" if world > 1 else "single",
+                "payload_bytes_rank0": C,
+                "compression_ratio_rank0": round(C / N, 4),
+                "max_code_len": int(plan.cb.max_len),
+            },
+            "step_schedule": "pipelined, one stream: batch k+1's histogram runs between batch k's pack and "
+                             "decode, so its host codebook and encode tables are built while batch k decodes; "
+                             + ("kernel_ms and host_* come from two further serialised steps; " if args.full else "")
+                             + "pack writes the "
+                             "block index and decode reads it, except for a FIXED16 codebook (every code 16 bits), "
+                             "whose decoder needs no index (hz_decode_indexless: symbol i at start + 16 i)",
+            "roundtrip_bit_exact": ok,
+            # algorithmic HBM bytes of one step per GPU: hist N + pack (N + C) + decode (C + N)
+            "step_algorithmic_GBps": round((3 * N + 2 * C) / (ms_step / 1e3) / 1e9, 1),
+            "step_hbm_frac": round((3 * N + 2 * C) / (ms_step / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
+        }
+
+    def finish(ok):
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if not ok:
+            sys.exit(3)
+
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the .compressed header, the packed
+        # payload (the bytes file_image() takes), the block index where pack wrote one, the decoded
+        # bytes, and the histogram the codebook came from
+        plan = state["plan"]
+        outputs = {"decoded": out[:2 * nsym], "header": state["header"], "histogram": codec.hist,
+                   "payload": state["payload"][:(plan.start_bit + plan.payload_bits + 7) // 8]}
+        if sidecar(plan, False):
+            from huffman_amd import index_bytes
+            outputs["index"] = state["index"].view(torch.uint8)[:index_bytes(nsym)]
+        dump_outputs(args.dump_outputs, outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
+
+    if not args.full:
+        if world > 1:
+            t = torch.tensor([elapsed, 0.0 if ok else 1.0], dtype=torch.float64, device=dev)
+            all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed, ok = float(t[0]), float(t[1]) == 0.0
+        if rank == 0:
+            print(json.dumps(headline(elapsed / args.steps * 1e3, state["plan"], ok)), flush=True)
+        finish(ok)
+        return
+
+    # --full from here on.
     # the drop-in file path, timed the same way: pack without an index, index-less decode
     log(f"rank {rank}: drop-in path (no index): {args.warmup} warmup + {args.steps} timed steps")
     out.fill_(0)
@@ -526,7 +639,6 @@ def main():
         elapsed, elapsed_dropin, bad = float(t[0]), float(t[1]), float(t[2])
         ok = bad == 0.0
     ms_step = elapsed / args.steps * 1e3
-    value = n_total / (ms_step / 1e3) / 1e9
     ms_dropin = elapsed_dropin / args.steps * 1e3
 
     if rank == 0:
@@ -560,36 +672,7 @@ def main():
         idx_algo = index_bytes(nsym) + (0 if fixed16 else C)
         idx_traffic = pmc_traffic("index")
         line = {
-            "metric": "encode + decode throughput GB/s and % HBM3E peak, 16 GiB Zipf(1.1), 1/2/4/8 GPU",
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": f"synthetic {args.dist} byte stream (splitmix64 seed 42, counter-based; rank g = bytes "
-                    f"[g*N,(g+1)*N) of one stream), generated in HBM",
-            "config": {
-                "workload": f"{N / 2**30:g} GiB {'Zipf(1.1)' if kind else 'uniform'} bytes per GPU: "
-                            "hist16 -> codebook -> pack -> decode, one global bit stream",
-                "bytes_per_gpu": N,
-                "total_bytes": n_total,
-                "symbols_per_gpu": nsym,
-                "parallelism": f"shard{world}" if world > 1 else "single",
-                "payload_bytes_rank0": C,
-                "compression_ratio_rank0": round(C / N, 4),
-                "max_code_len": int(plan.cb.max_len),
-            },
-            "step_schedule": "pipelined, one stream: batch k+1's histogram runs between batch k's pack and "
-                             "decode, so its host codebook and encode tables are built while batch k decodes; "
-                             "kernel_ms and host_* come from two further serialised steps; pack writes the "
-                             "block index and decode reads it, except for a FIXED16 codebook (every code 16 bits), "
-                             "whose decoder needs no index (hz_decode_indexless: symbol i at start + 16 i)",
-            "roundtrip_bit_exact": ok,
+            **headline(ms_step, plan, ok),
             "index_build_from_payload": index_build,
             "extract_indexless": extract,
             # the drop-in file path timed like the headline (same --steps / --warmup, same clock): pack
@@ -627,9 +710,6 @@ def main():
                     "algorithmic_bytes_per_launch": C + 2 * nsym,
                 },
             },
-            # algorithmic HBM bytes of one step per GPU: hist N + pack (N + C) + decode (C + N)
-            "step_algorithmic_GBps": round((3 * N + 2 * C) / (ms_step / 1e3) / 1e9, 1),
-            "step_hbm_frac": round((3 * N + 2 * C) / (ms_step / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
             "kernel_ms": {k: round(v, 4) for k, v in avg.items()},
             "kernel_GBps": {k: round(algo[k] / (avg[k] / 1e3) / 1e9, 1) for k in avg},
             "host_codebook_upload_ms": round(float(np.mean(host_ms)), 3),
@@ -702,11 +782,7 @@ def main():
             log("CPU baseline (reference baseline/ encoder + decoder)")
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample_mib << 20, kind, args.cpu_par_sample_mib << 20)
         print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if not ok:
-        sys.exit(3)
+    finish(ok)
 
 
 if __name__ == "__main__":

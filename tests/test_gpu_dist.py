@@ -123,7 +123,8 @@ def test_bench_rehearsal_three_ranks(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", "3", "--rehearse", "--size", str(96 << 20), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--gpus", "3", "--rehearse", "--size", str(96 << 20), "--steps", "2", "--warmup", "1",
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -152,7 +153,7 @@ def test_bench_rehearsal_eight_ranks_1gib_shards(tmp_path, dist_kind):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
            "--gpus", "8", "--rehearse", "--size", str((1 << 30) + 64), "--dist", dist_kind, "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
