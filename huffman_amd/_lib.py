@@ -13,6 +13,9 @@ BIN_DIR = os.path.join(_PKG, "bin")
 
 HZ_NSYM = 65536
 HZ_MAXLEN = 56
+HZ_RANGE_LEAD_BYTES = 32
+HZ_RANGE_TAIL_BYTES = 32
+HZ_RANGE_FULL_INDEX = 1
 
 STATUS = {
     0: "HZ_OK", -1: "HZ_EINVAL", -2: "HZ_ENOMEM", -3: "HZ_EHIP", -4: "HZ_ETOOLONG",
@@ -97,6 +100,10 @@ PROTOTYPES = [
     ("hz_last_pack_ranges", _I, [_P]),
     ("hz_decode", _I, [_P, _P, _U64, _U64, _P, _P]),
     ("hz_index_build", _I, [_P, _P, _U64, _U64, _U64, _P]),
+    ("hz_seek_bytes", _U64, [_U64]),
+    ("hz_seek_span", _I, [_P, _U64, _U64, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hz_decode_range", _I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _P, _U32]),
+    ("hz_index_expand", _I, [_P, _P, _U64, _P, _U64, _P]),
     ("hz_decode_indexless", _I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     ("hz_indexless_scan", _I, [_P, _P, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _P]),
     ("hz_indexless_refix", _I, [_P, _U64, _P]),
@@ -111,6 +118,8 @@ PROTOTYPES = [
     ("hz_encode_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_encoded_size", _I, [_P, _U64, ctypes.POINTER(_U64)]),
     ("hz_decode_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_seek_build_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_decode_range_host", _I, [_P, _U64, _P, _U64, _U64, _P]),
 ]
 
 _lib = None

@@ -145,6 +145,46 @@ def index_starts(index, nsym):
     return index[:nb + 1]
 
 
+def seek_bytes(nsym):
+    """Bytes of a stream's seek table: the first words (start[]) of its block index."""
+    return load().hz_seek_bytes(nsym)
+
+
+def seek_span(seek_host, nsym, sym_begin, sym_count):
+    """(byte_begin, byte_end) of the payload a range decode reads (hz_seek_span): host arithmetic."""
+    seek = np.ascontiguousarray(seek_host, dtype=np.uint64)
+    if seek.size * 8 < seek_bytes(nsym):
+        raise ValueError("seek table shorter than seek_bytes(nsym)")
+    b, e = ctypes.c_uint64(), ctypes.c_uint64()
+    check(load().hz_seek_span(seek.ctypes.data_as(ctypes.c_void_p), nsym, sym_begin, sym_count, ctypes.byref(b),
+                              ctypes.byref(e)), "hz_seek_span")
+    return b.value, e.value
+
+
+def build_seek(blob):
+    """.compressed image -> its seek table (uint64 start[nblocks + 1]; bits count from the file byte
+    that holds the first payload bit). Works on files the reference wrote."""
+    lib = load()
+    arr, p = _buf(blob)
+    _, info = parse_header(arr)
+    seek = np.zeros(max(seek_bytes(info.n // 2) // 8, 1), dtype=np.uint64)
+    nsym = ctypes.c_uint64()
+    check(lib.hz_seek_build_host(p, arr.size, seek.ctypes.data_as(ctypes.c_void_p), seek.size * 8, ctypes.byref(nsym)),
+          "hz_seek_build_host")
+    return seek[:seek_bytes(nsym.value) // 8]
+
+
+def decode_range(blob, seek, offset, length):
+    """Bytes [offset, offset + length) of the original from a .compressed image and its seek table."""
+    lib = load()
+    arr, p = _buf(blob)
+    sk = np.ascontiguousarray(seek, dtype=np.uint64)
+    out = np.empty(max(length, 1), dtype=np.uint8)
+    check(lib.hz_decode_range_host(p, arr.size, sk.ctypes.data_as(ctypes.c_void_p), offset, length,
+                                   out.ctypes.data_as(ctypes.c_void_p)), "hz_decode_range_host")
+    return out[:length].tobytes()
+
+
 class Device:
     """Stage API on device pointers (ints), stream-ordered on one HIP stream."""
 
@@ -220,6 +260,24 @@ class Device:
 
     def index_build(self, d_payload, payload_bytes, start_bit, nsym, d_index):
         check(self.lib.hz_index_build(self.h, d_payload, payload_bytes, start_bit, nsym, d_index), "hz_index_build")
+
+    # -- random access: seek table (the start[] words of a block index) and range decode ---------
+    def seek_span(self, seek_host, nsym, sym_begin, sym_count):
+        """Payload bytes (byte_begin, byte_end) a range decode of the symbols reads, margins included;
+        clamp byte_end to the payload. seek_host: the stream's start[] as a host uint64 array."""
+        return seek_span(seek_host, nsym, sym_begin, sym_count)
+
+    def decode_range(self, d_payload, payload_bytes, d_seek, nsym, sym_begin, sym_count, d_out, full_index=False,
+                     payload_byte_base=0):
+        """Symbols [sym_begin, sym_begin + sym_count) into d_out (2-byte aligned). d_payload holds the
+        payload bytes from payload_byte_base on; d_seek: the seek table, or a full block index."""
+        check(self.lib.hz_decode_range(self.h, d_payload, payload_bytes, payload_byte_base, d_seek, nsym, sym_begin,
+                                       sym_count, d_out, _lib.HZ_RANGE_FULL_INDEX if full_index else 0),
+              "hz_decode_range")
+
+    def index_expand(self, d_payload, payload_bytes, d_seek, nsym, d_index):
+        """Seek table -> the complete block index (d_seek may be d_index)."""
+        check(self.lib.hz_index_expand(self.h, d_payload, payload_bytes, d_seek, nsym, d_index), "hz_index_expand")
 
     def decode_indexless(self, d_payload, payload_bytes, start_bit, nsym, d_out, d_end_bit=None):
         """Decode an index-less stream (the `extract` path): no block index; d_end_bit (device u64) gets

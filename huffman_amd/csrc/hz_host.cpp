@@ -597,6 +597,62 @@ extern "C" int hz_index_build(hz_ctx* c, const uint8_t* d_payload, uint64_t payl
     return arm_err_check(c);
 }
 
+// ---- random access: seek table and range decode ----------------------------
+extern "C" uint64_t hz_seek_bytes(uint64_t nsym) { return nsym ? 8 * (index_blocks(nsym) + 1) : 0; }
+
+extern "C" int hz_seek_span(const uint64_t* seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                            uint64_t* byte_begin, uint64_t* byte_end) {
+    if (!byte_begin || !byte_end) return HZ_EINVAL;
+    if (sym_begin > nsym || sym_count > nsym - sym_begin) return HZ_EINVAL;
+    *byte_begin = *byte_end = 0;
+    if (sym_count == 0) return HZ_OK;
+    if (!seek) return HZ_EINVAL;
+    const uint64_t b0 = sym_begin / kBlockSyms, b1 = (sym_begin + sym_count - 1) / kBlockSyms;
+    const uint64_t first = seek[b0] / 8, last = seek[b1 + 1] / 8 + (seek[b1 + 1] % 8 ? 1 : 0);
+    if (last < first) return HZ_EINVAL;
+    // the staging window of a block starts 16 bytes below the 16-byte chunk of its first bit
+    // (dec_stage_prefetch / dec_stage_commit; the walk's reader starts at that chunk, br_init) and
+    // ends with the chunk two words past its last bit; the reader runs one chunk ahead
+    *byte_begin = first > kRangeLeadBytes ? (first - kRangeLeadBytes) & ~15ull : 0;
+    *byte_end = last + kRangeTailBytes;
+    return HZ_OK;
+}
+
+extern "C" int hz_decode_range(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t payload_byte_base,
+                               const uint64_t* d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                               uint8_t* d_out, uint32_t flags) {
+    if (!c || !d_payload || !d_seek || !d_out) return HZ_EINVAL;
+    if ((flags & ~HZ_RANGE_FULL_INDEX) || (((uintptr_t)d_out) & 1)) return HZ_EINVAL;
+    if (sym_begin > nsym || sym_count > nsym - sym_begin) return HZ_EINVAL;
+    if (sym_count == 0) return HZ_OK;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    int rc = ensure_scratch(c, range_scratch_words(sym_begin, sym_count));
+    if (rc) return rc;
+    HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 0));
+    HZ_TRY(launch_decode_range(c->t, d_payload, payload_bytes, payload_byte_base,
+                               reinterpret_cast<const unsigned long long*>(d_seek), nsym, sym_begin, sym_count, d_out,
+                               (flags & HZ_RANGE_FULL_INDEX) != 0, c->d_desc, c->d_err, c->ncu, c->stream));
+    HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 1));
+    c->ev_used[HZ_STAGE_DECODE] = true;
+    return arm_err_check(c);
+}
+
+extern "C" int hz_index_expand(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, const uint64_t* d_seek,
+                               uint64_t nsym, uint64_t* d_index) {
+    if (!c) return HZ_EINVAL;
+    if (nsym == 0) return HZ_OK;
+    if (!d_payload || !d_seek || !d_index) return HZ_EINVAL;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    HZ_TRY(stage_event(c, HZ_STAGE_INDEX, 0));
+    HZ_TRY(launch_index_expand(c->t, d_payload, payload_bytes, reinterpret_cast<const unsigned long long*>(d_seek), nsym,
+                               reinterpret_cast<unsigned long long*>(d_index), c->d_err, c->stream));
+    HZ_TRY(stage_event(c, HZ_STAGE_INDEX, 1));
+    c->ev_used[HZ_STAGE_INDEX] = true;
+    return arm_err_check(c);
+}
+
 extern "C" int hz_decode_indexless(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
                                    uint64_t nsym, uint8_t* d_out, uint64_t* d_end_bit) {
     if (!c) return HZ_EINVAL;
@@ -906,6 +962,79 @@ int decode_image(const uint8_t* f, uint64_t len, std::vector<uint8_t>& out) {
         if ((rc = hz_ctx_sync(c))) return rc;
     }
     if (info.is_odd) out[2 * nsym] = (uint8_t)info.last_byte;
+    return HZ_OK;
+}
+
+// The seek table of a complete .compressed image: hz_index_build's start[].
+int seek_build_image(const uint8_t* f, uint64_t len, uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym_out) {
+    std::unique_ptr<hz_codebook> cb(new hz_codebook());
+    hz_header_info info;
+    int rc = hz_header_parse(f, len, cb.get(), &info);
+    if (rc) return rc;
+    const uint64_t nsym = info.n / 2;
+    *nsym_out = nsym;
+    if (nsym == 0) return HZ_OK;
+    const uint64_t pay = len - info.payload_byte;
+    const uint64_t pay_bits = pay * 8 > info.payload_bit ? pay * 8 - info.payload_bit : 0;
+    if (nsym > pay_bits / std::max<uint32_t>(cb->min_len, 1)) return HZ_EFORMAT;
+    if (!seek || cap_bytes < hz_seek_bytes(nsym)) return HZ_ECAP;
+    hz_ctx* c;
+    if ((rc = default_ctx(&c))) return rc;
+    HZ_TRY(hipSetDevice(c->device));
+    if ((rc = hz_codebook_upload_decode(c, cb.get()))) return rc;
+    DevBuf dpay, didx;
+    if ((rc = dpay.alloc(pay + 16))) return rc;
+    HZ_TRY(hipMemsetAsync(dpay.p, 0, pay + 16, c->stream));
+    HZ_TRY(hipMemcpyAsync(dpay.p, f + info.payload_byte, pay, hipMemcpyHostToDevice, c->stream));
+    if ((rc = didx.alloc(hz_index_bytes(nsym)))) return rc;
+    if ((rc = hz_index_build(c, (const uint8_t*)dpay.p, pay, info.payload_bit, nsym, (uint64_t*)didx.p))) return rc;
+    HZ_TRY(hipMemcpyAsync(seek, didx.p, hz_seek_bytes(nsym), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = hz_ctx_sync(c))) return rc;
+    if (seek[index_blocks(nsym)] > pay * 8) return HZ_EFORMAT;  // fewer than nsym codewords in the payload
+    return HZ_OK;
+}
+
+// Bytes [offset, offset + count) of the original of a complete .compressed image, from its seek table.
+int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uint64_t offset, uint64_t count,
+                       uint8_t* out) {
+    std::unique_ptr<hz_codebook> cb(new hz_codebook());
+    hz_header_info info;
+    int rc = hz_header_parse(f, len, cb.get(), &info);
+    if (rc) return rc;
+    if (offset > info.n || count > info.n - offset) return HZ_EINVAL;
+    if (count == 0) return HZ_OK;
+    if (!out) return HZ_EINVAL;
+    const uint64_t nsym = info.n / 2, pay = len - info.payload_byte;
+    const uint64_t s0 = offset / 2, s1 = std::min((offset + count + 1) / 2, nsym);  // covering symbols
+    if (s1 > s0) {
+        if (!seek) return HZ_EINVAL;
+        uint64_t bb, be;
+        if ((rc = hz_seek_span(seek, nsym, s0, s1 - s0, &bb, &be))) return rc;
+        if (bb >= pay) return HZ_EFORMAT;
+        be = std::min(be, pay);
+        const uint64_t b0 = s0 / kBlockSyms, b1 = (s1 - 1) / kBlockSyms;
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload_decode(c, cb.get()))) return rc;
+        DevBuf dpay, dseek, dout;
+        if ((rc = dpay.alloc(be - bb + 16))) return rc;
+        HZ_TRY(hipMemsetAsync(dpay.p, 0, be - bb + 16, c->stream));
+        HZ_TRY(hipMemcpyAsync(dpay.p, f + info.payload_byte + bb, be - bb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = dseek.alloc(8 * (b1 - b0 + 2)))) return rc;
+        HZ_TRY(hipMemcpyAsync(dseek.p, seek + b0, 8 * (b1 - b0 + 2), hipMemcpyHostToDevice, c->stream));
+        if ((rc = dout.alloc(2 * (s1 - s0)))) return rc;
+        // the device reads entries b0 .. b1 + 1 only, addressed from entry 0
+        const uint64_t* d_seek0 = (const uint64_t*)dseek.p - b0;
+        if ((rc = hz_decode_range(c, (const uint8_t*)dpay.p, be - bb, bb, d_seek0, nsym, s0, s1 - s0, (uint8_t*)dout.p, 0)))
+            return rc;
+        std::vector<uint8_t> tmp(2 * (s1 - s0));
+        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp.size(), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+        const uint64_t skip = offset - 2 * s0;
+        memcpy(out, tmp.data() + skip, std::min<uint64_t>(count, tmp.size() - skip));
+    }
+    if (info.is_odd && offset + count == info.n) out[count - 1] = (uint8_t)info.last_byte;
     return HZ_OK;
 }
 
@@ -1706,6 +1835,17 @@ static int hz_decode_host_impl(const uint8_t* file, uint64_t len, uint8_t* out, 
 
 extern "C" int hz_decode_host(const uint8_t* file, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* out_n) {
     return guarded([&] { return hz_decode_host_impl(file, len, out, cap, out_n); });
+}
+
+extern "C" int hz_seek_build_host(const uint8_t* file, uint64_t len, uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym) {
+    if (!file || !nsym) return HZ_EINVAL;
+    return guarded([&] { return seek_build_image(file, len, seek, cap_bytes, nsym); });
+}
+
+extern "C" int hz_decode_range_host(const uint8_t* file, uint64_t len, const uint64_t* seek, uint64_t offset,
+                                    uint64_t count, uint8_t* out) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&] { return decode_range_image(file, len, seek, offset, count, out); });
 }
 
 // Compressor.cu:315-632, stdout lines kept (:335-336,385,612-631).

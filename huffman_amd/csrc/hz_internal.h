@@ -239,6 +239,17 @@ hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t pay
                          uint64_t nsym, const unsigned long long* d_index, uint8_t* d_out,
                          uint32_t* d_err, int ncu, hipStream_t s,
                          uint64_t start0 = 0);  // d_index null (FIXED16 only): symbol i at start0 + 16 i
+// Random access (DESIGN.md "Random access"). d_seek: the stream's start[] (a full index when full_index);
+// d_payload holds the stream's payload bytes [base, base + payload_bytes); d_scratch: range_scratch_words().
+constexpr uint64_t kRangeLeadBytes = HZ_RANGE_LEAD_BYTES, kRangeTailBytes = HZ_RANGE_TAIL_BYTES;
+uint64_t range_scratch_words(uint64_t sym_begin, uint64_t sym_count);
+hipError_t launch_decode_range(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t base,
+                               const unsigned long long* d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                               uint8_t* d_out, bool full_index, unsigned long long* d_scratch, uint32_t* d_err, int ncu,
+                               hipStream_t s);
+hipError_t launch_index_expand(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
+                               const unsigned long long* d_seek, uint64_t nsym, unsigned long long* d_index,
+                               uint32_t* d_err, hipStream_t s);
 hipError_t launch_index_build(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                               uint64_t start_bit, uint64_t nsym, unsigned long long* d_index,
                               unsigned long long* d_scratch, uint32_t* d_err, uint32_t* h_scratch, int ncu,

@@ -1795,8 +1795,8 @@ HZ_DEV void dec_store(const DecArgs& a, uint64_t b, int lane, const uint32_t* pk
 // One wave decodes NB blocks at once (NB * kChainsPerLane independent chains
 // per lane: every table wait covers more symbols). Block g of the group uses
 // staging slot g. Blocks past the stream's end decode nothing.
-template <int MODE, bool WIDE, int NB>
-HZ_DEV void dec_group(const DecArgs& a, const uint32_t* lds, uint32_t* stg0, uint32_t slot, uint64_t bfirst,
+template <int MODE, bool WIDE, int NB, typename A>
+HZ_DEV void dec_group(const A& a, const uint32_t* lds, uint32_t* stg0, uint32_t slot, uint64_t bfirst,
                       int lane) {
     constexpr int C1 = kChainsPerLane;
     constexpr int C = NB * C1;
@@ -2100,7 +2100,8 @@ constexpr int kPfStep = 4;  // chain step at which the next block's staging load
 // Persistent pipelined decoder of one wave: blocks b, b + stride, ... The
 // staging chunks of the next block and the metadata of the one after are
 // loaded halfway through this block's steps, so no block waits on HBM.
-HZ_DEV void dec_wave_pipe(const DecArgs& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
+template <typename A>
+HZ_DEV void dec_wave_pipe(const A& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
                           uint64_t stride, int lane) {
     const uint32_t* l2g = a.l2;
     constexpr int C = kChainsPerLane;
@@ -2163,7 +2164,8 @@ HZ_DEV void dec_wave_pipe(const DecArgs& a, const uint32_t* lds, uint32_t* stg, 
 // lookups are consumed after the other three pairs' LDS walks, so a gather
 // has three walks to land in instead of one. Half as many waves (two staging
 // slots each) hold the same LDS; blocks b, b + 1, then b + stride, ...
-HZ_DEV void dec_wave_pipe2(const DecArgs& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
+template <typename A>
+HZ_DEV void dec_wave_pipe2(const A& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
                            uint64_t stride, int lane) {
     constexpr int C = 2 * kChainsPerLane;
     static_assert(kChainsPerLane == 4, "four pairs of chains over two blocks");
@@ -2409,10 +2411,20 @@ static void fill_dec_args(DecArgs& a, const Tables& t, const uint8_t* d_payload,
 // index's max_bits and idles the waves that do not get one. Up to two
 // workgroups per CU (each holds its own table copy): whichever shape runs
 // more waves.
+struct RangeDecArgs;
 template <int MODE, bool WIDE, int PIPE>
-static hipError_t run_decode(const DecArgs& a, uint64_t payload_bits, int ncu, hipStream_t s) {
+__global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode_range(RangeDecArgs a);  // below
+template <int MODE, bool WIDE, int PIPE, typename A>
+static const void* decode_fn() {
+    if constexpr (std::is_same<A, DecArgs>::value) return (const void*)k_decode<MODE, WIDE, PIPE>;
+    else return (const void*)k_decode_range<MODE, WIDE, PIPE>;
+}
+
+template <int MODE, bool WIDE, int PIPE, typename A = DecArgs>
+static hipError_t run_decode(const A& a, uint64_t payload_bits, int ncu, hipStream_t s) {
+    const void* fn = decode_fn<MODE, WIDE, PIPE, A>();
     {
-        hipError_t e = ensure_lds_limit((const void*)k_decode<MODE, WIDE, PIPE>, kLdsBytes);
+        hipError_t e = ensure_lds_limit(fn, kLdsBytes);
         if (e != hipSuccess) return e;
     }
     // a block never exceeds 2048 x max_len bits, whatever follows the stream in the buffer
@@ -2433,7 +2445,7 @@ static hipError_t run_decode(const DecArgs& a, uint64_t payload_bits, int ncu, h
         if (g * w > best_g * best_w) { best_w = w; best_g = g; }
     }
     if (best_w == 0) return hipErrorInvalidValue;
-    DecArgs b = a;
+    A b = a;
     b.region_words = (uint32_t)best_w * est;
     if (b.region_words < worst && table + worst <= kLdsBytes / 4) b.region_words = worst;  // any stream decodes
     if (table + b.region_words > kLdsBytes / 4 / (uint32_t)best_g) best_g = 1;
@@ -2446,8 +2458,8 @@ static hipError_t run_decode(const DecArgs& a, uint64_t payload_bits, int ncu, h
     const int threads = PIPE == 2 ? (64 * ((best_w + 1) / 2) < kDecPipe2Threads ? 64 * ((best_w + 1) / 2)
                                                                                  : kDecPipe2Threads)
                                   : 64 * best_w;
-    hipLaunchKernelGGL((k_decode<MODE, WIDE, PIPE>), dim3(wgs), dim3(threads), lds, s, b);
-    return hipGetLastError();
+    void* kargs[] = {&b};
+    return hipLaunchKernel(fn, dim3(wgs), dim3(threads), kargs, lds, s);
 }
 
 hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t nsym,
@@ -4549,6 +4561,357 @@ hipError_t chain_decode(ChainState* st, const Tables& t, uint64_t nsym, uint8_t*
     }
     cap_check(s, "tail+end");
     return hipGetLastError();
+}
+
+// ===========================================================================
+// Random access (hz_decode_range, hz_index_expand; DESIGN.md "Random access").
+// The seek table is start[] alone. A range of symbols is decoded in TILES of
+// whole blocks: per tile one pass checks every block's bounds and, from the
+// seek table, walks its codewords to rebuild the sub row (one lane per block:
+// the walk is serial in a block and independent across blocks); then the block
+// decoders of k_decode run over the tile through a small index of the tile in
+// scratch (start[] clamped into the payload view, the tile's max_bits, the sub
+// rows) with a store clipped to the range. Blocks that fail a check are flagged
+// and never stored. The payload view may be a slice of the stream: bits stay
+// stream bits, the view's word 0 is moved down instead (never dereferenced below
+// w_first).
+// ===========================================================================
+struct RangeDecArgs : DecArgs {
+    uint64_t w_first;    // first word of the view that exists (words below it are only addressed, never read)
+    const uint8_t* bad;  // per tile block: nonzero = failed a check, nothing is stored for it
+    uint64_t blk0;       // the tile's first block in the stream (a.starts / a.subs / a.nblocks are the tile's)
+    uint64_t lo, hi;     // stream symbols [lo, hi) go to out + 2 (sym - lo); nothing else is written
+};
+
+// dec_stage_prefetch for a moved view: chunks outside the payload read the view's first real chunk
+// (dec_stage_commit zero-fills them as it does for the plain view's word 0).
+HZ_DEV void dec_stage_prefetch(const RangeDecArgs& a, const PipeMeta& m, int lane, uint4 (&v)[kStageUnroll]) {
+    const uint64_t w0 = (((m.b0 + a.bit_adj) >> 5) & ~3ull) - 4;
+#pragma unroll
+    for (int u = 0; u < kStageUnroll; ++u) {
+        const uint64_t w = w0 + 4ull * ((uint32_t)lane + (uint32_t)u * kWave);
+        const bool in = w < a.nwords && w >= a.w_first;
+        const uint64_t wl = !in ? a.w_first : (w + 4 <= a.nwords ? w : a.nwords - 4);
+        v[u] = *reinterpret_cast<const uint4*>(a.words + wl);
+    }
+}
+
+// dec_store clipped to [lo, hi): whole blocks inside the range as chain_store writes them (16-byte
+// non-temporal stores at a 2-byte aligned address), edge blocks symbol by symbol.
+HZ_DEV void dec_store(const RangeDecArgs& a, uint64_t b, int lane, const uint32_t* pk) {
+    if (a.bad[b]) return;
+    const uint64_t sym0 = (a.blk0 + b) * kBlockSyms;
+    uint16_t* out16 = reinterpret_cast<uint16_t*>(a.out);
+    if (sym0 >= a.lo && sym0 + kBlockSyms <= a.hi) {
+        uint16_t* ob = out16 + (sym0 - a.lo);
+#pragma unroll
+        for (int c = 0; c < kChainsPerLane; ++c) {
+            u32x4a2 v = u32x4a2{pk[4 * c], pk[4 * c + 1], pk[4 * c + 2], pk[4 * c + 3]};
+            __builtin_nontemporal_store(v, reinterpret_cast<u32x4a2*>(ob + kChainSyms * (kWave * c + lane)));
+        }
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < kChainsPerLane; ++c) {
+        const uint64_t s0 = sym0 + (uint64_t)kChainSyms * (uint32_t)(c * kWave + lane);
+        for (uint32_t q = 0; q < (uint32_t)kChainSyms; ++q) {
+            const uint64_t sy = s0 + q;
+            if (sy >= a.lo && sy < a.hi) out16[sy - a.lo] = (uint16_t)(pk[4 * c + (q >> 1)] >> (16 * (q & 1)));
+        }
+    }
+}
+
+template <int MODE, bool WIDE, int PIPE>
+__global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode_range(RangeDecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    copy_lds_table(lds, a.lds_img, a.lds_words);
+    const int lane = threadIdx.x & 63;
+    const uint32_t wid = wave_id();
+    // slots fit the stream's largest block; waves without a slot have nothing to do
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)dec_slot_words(a.starts[a.nblocks + 1], a.max_len));
+    const uint32_t nwave = blockDim.x >> 6;
+    if constexpr (PIPE == 2) {
+        uint32_t nw2 = a.region_words / (2 * slot);
+        nw2 = nw2 < nwave ? nw2 : nwave;
+        if (nw2 > 0) {  // else one block per wave below (a stream whose largest block needs more)
+            if (wid >= nw2) return;
+            const uint64_t b = 2 * ((uint64_t)blockIdx.x * nw2 + wid), stride = 2 * (uint64_t)gridDim.x * nw2;
+            dec_wave_pipe2(a, lds, lds + a.lds_words + wid * 2 * slot, slot, b, stride, lane);
+            return;
+        }
+    }
+    uint32_t nw = a.region_words / slot;
+    nw = nw < nwave ? nw : nwave;
+    if (wid >= nw) return;
+    uint32_t* stg = lds + a.lds_words + wid * slot;
+    const uint64_t b = (uint64_t)blockIdx.x * nw + wid, stride = (uint64_t)gridDim.x * nw;
+    if constexpr (PIPE != 0) {
+        dec_wave_pipe(a, lds, stg, slot, b, stride, lane);
+    } else {
+        for (uint64_t bb = b; bb < a.nblocks; bb += stride) dec_group<MODE, WIDE, 1>(a, lds, stg, slot, bb, lane);
+    }
+}
+
+struct SeekArgs {
+    const unsigned long long* seek;  // the stream's start[]: block b at seek[b]
+    const unsigned long long* isub;  // a full index's sub rows (chain 0 is checked against start[b]); else null
+    unsigned long long* tstart;      // the tile's index in scratch: start[nb + 1] clamped into the view; null: none
+    unsigned long long* rows;        // sub rows out, 64 words per block of the tile
+    unsigned long long* maxp;        // the tile's largest block in bits (atomicMax; zeroed by the launcher)
+    uint8_t* bad;                    // per block of the tile; null: none
+    uint64_t blk0, nb, nsym;
+    uint64_t clamp_lo, bit_hi;       // stream bits a block may start at / end at inside the view
+};
+
+constexpr int kSeekThreads = 256;
+
+// One lane per block of the tile. Checks: start[b] <= start[b + 1] and at most cnt * max_len bits apart
+// (else format), the staging window inside the view (else invalid argument). WALK: the block's cnt
+// codewords from start[b] must end exactly at start[b + 1]; every 8th one's low 16 bits go to the sub
+// row (chain c of the block at u16 c, as hz_pack writes it), chains past the stream's end = the end bit.
+// The walk stops at cnt codewords or past start[b + 1], whichever comes first, and the reader clamps
+// its loads to the view.
+template <int MODE, bool WALK>
+__global__ __launch_bounds__(kSeekThreads) void k_seek_subs(DecArgs a, SeekArgs y) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    if constexpr (WALK && MODE != DEC_FIXED16) copy_lds_table(lds, a.lds_img, a.lds_words);
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long mx = 0;
+    if (j < y.nb) {
+        const uint64_t b = y.blk0 + j;
+        const uint64_t s0 = y.seek[b], s1 = y.seek[b + 1];
+        const uint64_t left = y.nsym - b * kBlockSyms;
+        const uint32_t cnt = left < (uint64_t)kBlockSyms ? (uint32_t)left : (uint32_t)kBlockSyms;
+        uint32_t err = 0;
+        if (s1 < s0 || s1 - s0 > (uint64_t)cnt * (uint32_t)a.max_len) err = 1u;
+        else if (s0 < y.clamp_lo || s1 > y.bit_hi) err = 16u;
+        else if (y.isub && (uint32_t)(y.isub[b * kWave] & 0xffffu) != (uint32_t)(s0 & 0xffffu)) err = 1u;
+        if (y.tstart) {
+            auto clamp = [&](uint64_t x) { return x < y.clamp_lo ? y.clamp_lo : (x > y.bit_hi ? y.bit_hi : x); };
+            y.tstart[j] = clamp(s0);
+            if (j + 1 == y.nb) y.tstart[y.nb] = clamp(s1);
+        }
+        if (WALK && !err) {
+            unsigned long long* row = y.rows + j * kWave;
+            unsigned long long acc = 0;
+            auto put = [&](uint32_t ch, uint64_t pos) {
+                acc |= (unsigned long long)(pos & 0xffffu) << (16 * (ch & 3));
+                if ((ch & 3) == 3) { row[ch >> 2] = acc; acc = 0; }
+            };
+            if constexpr (MODE == DEC_FIXED16) {
+                if (s1 - s0 != 16ull * cnt) {
+                    err = 1u;
+                } else {
+                    for (uint32_t ch = 0; ch < (uint32_t)kChainsPerBlock; ++ch)
+                        put(ch, ch * kChainSyms < cnt ? s0 + 16ull * kChainSyms * ch : s1);
+                }
+            } else {
+                BitReader r;
+                br_init(r, a, s0 + a.bit_adj);
+                uint64_t pos = s0;
+                uint32_t i = 0;
+                for (; i < cnt; ++i) {
+                    if ((i & (kChainSyms - 1)) == 0) put(i / kChainSyms, pos);
+                    uint32_t sym;
+                    const uint32_t L = br_next<MODE>(r, a, lds, sym);
+                    pos += L;
+                    if (L == 0 || pos > s1) break;
+                }
+                if (i < cnt || pos != s1) {
+                    err = 1u;
+                } else {
+                    for (uint32_t ch = (cnt + kChainSyms - 1) / kChainSyms; ch < (uint32_t)kChainsPerBlock; ++ch) put(ch, s1);
+                }
+            }
+        }
+        if (y.bad) y.bad[j] = (uint8_t)(err != 0);
+        if (err) atomicOr(a.err, err);
+        else mx = s1 - s0;
+    }
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t lo = shfl_xor_u32((uint32_t)mx, m), hi = shfl_xor_u32((uint32_t)(mx >> 32), m);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(y.maxp, mx);
+}
+
+// FIXED16 range: symbol s of block b sits at start[b] + 16 (s - 2048 b); a thread decodes 8 symbols.
+__global__ __launch_bounds__(1024) void k_range_fixed16(RangeDecArgs a, SeekArgs y) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    copy_lds_table(lds, a.lds_img, a.lds_words);
+    const uint16_t* t16 = reinterpret_cast<const uint16_t*>(lds);
+    const uint64_t b = a.lo / kBlockSyms, cnt = a.hi - a.lo;
+    const uint64_t sb = y.seek[b];
+    const uint64_t p = sb + 16 * (a.lo - b * kBlockSyms);
+    if (sb < y.clamp_lo || sb > y.bit_hi || p > y.bit_hi || 16 * cnt > y.bit_hi - p) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.err, 16u);
+        return;
+    }
+    uint16_t* out16 = reinterpret_cast<uint16_t*>(a.out);
+    const uint64_t ng = (cnt + kChainSyms - 1) / kChainSyms, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < ng; g += stride) {
+        const uint64_t P = p + 16ull * kChainSyms * g + a.bit_adj;
+        const uint64_t W = P >> 5;
+        const uint32_t sh = (uint32_t)(P & 31);
+        uint32_t w[5], o[4];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) w[k] = W + k < a.nwords ? bswap32(a.words[W + k]) : 0u;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const uint32_t cw = sh ? __builtin_amdgcn_alignbit(w[t], w[t + 1], 32u - sh) : w[t];
+            o[t] = (uint32_t)t16[cw >> 16] | ((uint32_t)t16[cw & 0xffffu] << 16);
+        }
+        const uint64_t s0 = g * kChainSyms;
+        if (s0 + kChainSyms <= cnt) {
+            *reinterpret_cast<u32x4a2*>(out16 + s0) = u32x4a2{o[0], o[1], o[2], o[3]};
+        } else {
+            for (uint32_t q = 0; s0 + q < cnt; ++q) out16[s0 + q] = (uint16_t)(o[q >> 1] >> (16 * (q & 1)));
+        }
+    }
+}
+
+// Blocks per tile: 131 072 (256 MiB of output) give the one-lane-per-block walk 8 waves on each of
+// 256 CUs and keep the scratch at 65 MiB whatever the range. HZ_RANGE_TILE_BLOCKS (read once) overrides.
+// With a full index a tile keeps 9 bytes per block instead of 521 (no sub rows), so its tiles are
+// kRangeFullTileFactor times as long: every tile costs a launch prologue and tail (about 45 us measured).
+constexpr uint64_t kRangeTileBlocks = 131072;
+constexpr uint64_t kRangeFullTileFactor = 16;
+static uint64_t range_tile_blocks() {
+    static const uint64_t v = [] {
+        const char* e = getenv("HZ_RANGE_TILE_BLOCKS");
+        const long long x = e ? atoll(e) : 0;
+        return x > 0 ? (uint64_t)x : kRangeTileBlocks;
+    }();
+    return v;
+}
+
+uint64_t range_scratch_words(uint64_t sym_begin, uint64_t sym_count) {
+    if (!sym_count) return 0;
+    const uint64_t nb = (sym_begin + sym_count - 1) / kBlockSyms - sym_begin / kBlockSyms + 1;
+    const uint64_t T = nb < range_tile_blocks() ? nb : range_tile_blocks();
+    const uint64_t Tf = nb < kRangeFullTileFactor * range_tile_blocks() ? nb : kRangeFullTileFactor * range_tile_blocks();
+    const uint64_t seek = (T + 2) + (T + 7) / 8 + (uint64_t)kWave * T, full = (Tf + 2) + (Tf + 7) / 8;
+    return seek > full ? seek : full;  // either mode, so a context's scratch settles after one call
+}
+
+// The view of a payload slice that holds stream bytes [base, base + payload_bytes): stream bit p is
+// bit p + bit_adj of `words`, whose word 0 lies below the slice when base > 0.
+static void fill_range_view(RangeDecArgs& a, SeekArgs& y, const Tables& t, const uint8_t* d_payload,
+                            uint64_t payload_bytes, uint64_t base, uint64_t nsym) {
+    fill_dec_args(a, t, d_payload, payload_bytes, nsym);
+    const uint64_t head = (uintptr_t)d_payload & 63, r = base & 63;
+    uint64_t shift = base >> 6;  // 64-byte units the view's word 0 moves down
+    uint64_t adj = head - r;
+    if (head < r) { adj = head + 64 - r; shift += 1; }
+    a.words = reinterpret_cast<const uint32_t*>(((uintptr_t)d_payload & ~(uintptr_t)63) - 64 * shift);
+    a.bit_adj = (uint32_t)(8 * adj);
+    a.w_first = 16 * shift;
+    a.nwords = a.w_first + (payload_bytes + head + 3) / 4;
+    a.start0 = 0;
+    // a block's staging window starts 16 bytes below the 16-byte chunk of its first bit: inside the slice
+    // unless the slice starts the stream (base 0: words below the payload read as zeros, as in hz_decode)
+    const uint64_t vlo = 8 * base + a.bit_adj;
+    y.clamp_lo = base ? 128 * ((vlo + 127) / 128 + 1) - a.bit_adj : 0;
+    y.bit_hi = 8 * (base + payload_bytes);
+    if (y.clamp_lo > y.bit_hi) y.clamp_lo = y.bit_hi;  // a slice too small for any block: every block fails
+    y.nsym = nsym;
+}
+
+static int dec_pipe_mode() {
+    static const int v = [] { const char* e = getenv("HZ_DEC_PIPE"); return e ? atoi(e) : 2; }();
+    return v;
+}
+
+template <int MODE, bool WALK>
+static hipError_t seek_subs_launch(const Tables& t, const DecArgs& a, const SeekArgs& y, hipStream_t s) {
+    const uint32_t lds = WALK && MODE != DEC_FIXED16 ? t.dec_lds_bytes : 0;
+    hipError_t e = ensure_lds_limit((const void*)k_seek_subs<MODE, WALK>, kLdsBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_seek_subs<MODE, WALK>), dim3((y.nb + kSeekThreads - 1) / kSeekThreads), dim3(kSeekThreads), lds, s,
+                       a, y);
+    return hipGetLastError();
+}
+
+static hipError_t seek_walk_launch(const Tables& t, const DecArgs& a, const SeekArgs& y, hipStream_t s) {
+    if (t.dec_mode == DEC_FIXED16) return seek_subs_launch<DEC_FIXED16, true>(t, a, y, s);
+    if (t.dec_mode == DEC_DENSE) return seek_subs_launch<DEC_DENSE, true>(t, a, y, s);
+    return seek_subs_launch<DEC_LUT, true>(t, a, y, s);
+}
+
+hipError_t launch_decode_range(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t base,
+                               const unsigned long long* d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                               uint8_t* d_out, bool full_index, unsigned long long* d_scratch, uint32_t* d_err, int ncu,
+                               hipStream_t s) {
+    if (sym_count == 0) return hipSuccess;
+    RangeDecArgs a{};
+    SeekArgs y{};
+    fill_range_view(a, y, t, d_payload, payload_bytes, base, nsym);
+    a.out = d_out; a.err = d_err;
+    a.lo = sym_begin; a.hi = sym_begin + sym_count;
+    y.seek = d_seek;
+    hipError_t e;
+    if (t.dec_mode == DEC_FIXED16) {
+        if ((e = ensure_lds_limit((const void*)k_range_fixed16, kFixed16LdsBytes)) != hipSuccess) return e;
+        uint64_t wgs = ((sym_count + kChainSyms - 1) / kChainSyms + 1023) / 1024;
+        if (wgs > (uint64_t)ncu) wgs = ncu;
+        hipLaunchKernelGGL(k_range_fixed16, dim3(wgs), dim3(1024), kFixed16LdsBytes, s, a, y);
+        return hipGetLastError();
+    }
+    const uint64_t nblk = index_blocks(nsym);
+    y.isub = full_index ? d_seek + index_sub_offset(nblk) : nullptr;
+    const uint64_t bf = sym_begin / kBlockSyms, bl = (sym_begin + sym_count - 1) / kBlockSyms;
+    const uint64_t tile = (full_index ? kRangeFullTileFactor : 1) * range_tile_blocks();
+    const uint64_t T = bl - bf + 1 < tile ? bl - bf + 1 : tile;
+    y.tstart = d_scratch;
+    y.bad = reinterpret_cast<uint8_t*>(d_scratch + T + 2);
+    y.rows = d_scratch + (T + 2) + (T + 7) / 8;
+    const bool wide = t.dec_max_len > 32;
+    const bool piped = dec_pipe_mode() && t.dec_max_len <= t.dec_k + t.dec_level_bits && a.nwords - a.w_first >= 4;
+    const double avg = t.dec_avg_bits > (double)t.dec_min_len ? t.dec_avg_bits : (double)(t.dec_min_len > 0 ? t.dec_min_len : 1);
+    for (uint64_t tb = bf; tb <= bl; tb += T) {
+        const uint64_t nb = bl - tb + 1 < T ? bl - tb + 1 : T;
+        y.blk0 = tb; y.nb = nb;
+        y.maxp = y.tstart + nb + 1;
+        if ((e = hipMemsetAsync(y.maxp, 0, 8, s)) != hipSuccess) return e;
+        e = full_index ? seek_subs_launch<DEC_LUT, false>(t, a, y, s) : seek_walk_launch(t, a, y, s);
+        if (e != hipSuccess) return e;
+        a.starts = y.tstart;
+        a.subs = full_index ? y.isub + tb * kWave : y.rows;
+        a.nblocks = nb;
+        a.nsym = nb * kBlockSyms;
+        a.blk0 = tb;
+        a.bad = y.bad;
+        const uint64_t pbits = (uint64_t)(avg * (double)kBlockSyms * (double)nb);
+        if (t.dec_mode == DEC_DENSE) e = run_decode<DEC_DENSE, false, 0>(a, pbits, ncu, s);
+        else if (wide) e = run_decode<DEC_LUT, true, 0>(a, pbits, ncu, s);
+        else if (piped) e = dec_pipe_mode() == 1 ? run_decode<DEC_LUT, false, 1>(a, pbits, ncu, s)
+                                                 : run_decode<DEC_LUT, false, 2>(a, pbits, ncu, s);
+        else e = run_decode<DEC_LUT, false, 0>(a, pbits, ncu, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_index_expand(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
+                               const unsigned long long* d_seek, uint64_t nsym, unsigned long long* d_index,
+                               uint32_t* d_err, hipStream_t s) {
+    if (nsym == 0) return hipSuccess;
+    const uint64_t nblk = index_blocks(nsym);
+    hipError_t e;
+    if (d_seek != d_index &&
+        (e = hipMemcpyAsync(d_index, d_seek, 8 * (nblk + 1), hipMemcpyDeviceToDevice, s)) != hipSuccess)
+        return e;
+    if ((e = hipMemsetAsync(d_index + nblk + 1, 0, 8, s)) != hipSuccess) return e;
+    RangeDecArgs a{};
+    SeekArgs y{};
+    fill_range_view(a, y, t, d_payload, payload_bytes, 0, nsym);
+    a.err = d_err;
+    y.seek = d_index;
+    y.rows = d_index + index_sub_offset(nblk);
+    y.maxp = d_index + nblk + 1;
+    y.blk0 = 0; y.nb = nblk;
+    return seek_walk_launch(t, a, y, s);
 }
 
 }  // namespace hz

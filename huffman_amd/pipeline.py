@@ -155,6 +155,19 @@ class StreamCodec:
         self.dev.decode(payload.data_ptr(), payload.numel(), nsym, index.data_ptr(), out.data_ptr())
         return out
 
+    def decode_range(self, payload, nsym, index, sym_begin, sym_count, out, full_index=True, payload_byte_base=0):
+        """Symbols [sym_begin, sym_begin + sym_count) into `out` (2-byte aligned, 2 * sym_count bytes).
+        index: the block index (full_index=True) or only its start[] words, the seek table;
+        payload: the payload from payload_byte_base on (0: all of it, else Device.seek_span's bytes)."""
+        self.dev.decode_range(payload.data_ptr(), payload.numel(), index.data_ptr(), nsym, sym_begin, sym_count,
+                              out.data_ptr(), full_index, payload_byte_base)
+        return out
+
+    def index_expand(self, payload, nsym, seek, index):
+        """The complete block index from the seek table (seek may be index itself)."""
+        self.dev.index_expand(payload.data_ptr(), payload.numel(), seek.data_ptr(), nsym, index.data_ptr())
+        return index
+
     def sync(self):
         self.dev.sync()
 

@@ -218,6 +218,74 @@ int hz_decode(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uin
 int hz_index_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
                    uint64_t nsym, uint64_t *d_index);
 
+/* ---- random access: seek table and range decode ---------------------------
+ * A stream's SEEK TABLE is u64 start[nblocks + 1], the first nblocks + 1 words
+ * of its block index (so a block-index pointer is a valid seek-table pointer):
+ * the start bit of every 2048-symbol (4 KiB of output) block, then the
+ * stream's end bit; 8 bytes per 4 KiB of output. Bits count from byte 0 of the
+ * stream's payload buffer, as in the index. To keep one: hz_pack (or
+ * hz_index_build) into an index buffer, copy its first hz_seek_bytes(nsym)
+ * bytes to the host and store them beside the stream. To read symbols back:
+ * load the table, ask hz_seek_span which payload bytes the range needs, put
+ * those bytes (or the whole payload) and the table on the device, upload the
+ * codebook (hz_codebook_upload_decode) and call hz_decode_range. */
+#define HZ_RANGE_LEAD_BYTES 32  /* payload bytes kept before the first block's start byte */
+#define HZ_RANGE_TAIL_BYTES 32  /* payload bytes kept after the last block's end byte */
+#define HZ_RANGE_FULL_INDEX 1u  /* hz_decode_range flag: d_seek is a complete block index */
+
+uint64_t hz_seek_bytes(uint64_t nsym);            /* 8 * (nblocks + 1); 0 for nsym 0 */
+
+/* Host arithmetic on a HOST seek table: the payload bytes [*byte_begin, *byte_end)
+ * a range decode of symbols [sym_begin, sym_begin + sym_count) reads, margins
+ * included (HZ_RANGE_LEAD_BYTES before the first block's start byte, or the
+ * stream's byte 0; HZ_RANGE_TAIL_BYTES after the last block's end byte, which the
+ * caller clamps to the payload it has). byte_begin is a multiple of 16. Only
+ * seek[b0 .. b1 + 1] of the range's blocks are read. sym_count 0 gives an empty
+ * span (0, 0); sym_begin + sym_count > nsym or a descending table HZ_EINVAL. */
+int hz_seek_span(const uint64_t *seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                 uint64_t *byte_begin, uint64_t *byte_end);
+
+/* Decode symbols [sym_begin, sym_begin + sym_count) of a stream into d_out
+ * (2 * sym_count bytes, 2-byte aligned). Nothing outside those bytes is written.
+ * d_seek: the stream's seek table on the device (entries b0 .. b1 + 1 of the
+ * range's blocks are read, addressed from d_seek[0]). d_payload holds the stream's
+ * payload bytes [payload_byte_base, payload_byte_base + payload_bytes): the
+ * whole payload (base 0) or any slice that covers hz_seek_span's bytes, clamped
+ * to the payload's end (bytes past it read as zeros). Keep d_payload congruent to
+ * payload_byte_base modulo 16 or better, as hipMalloc'd buffers with
+ * hz_seek_span's byte_begin are.
+ * flags: HZ_RANGE_FULL_INDEX = d_seek is a complete format-2 block index of the
+ * stream, so sub[] is read from it and no walk runs.
+ * Needs the decode tables only (hz_codebook_upload_decode). Stream-ordered on the
+ * context's stream and capturable by a HIP graph; the host waits only when the
+ * context's scratch must grow (at most 65 MiB whatever the range: long ranges
+ * run as tiles of 131 072 blocks, a walk and a decode per tile; 16 times as
+ * many blocks per tile with a full index, which needs no sub[] rows). Ends a pending
+ * index-less part like every scratch user.
+ * HZ_EINVAL at the call: null pointers, sym_begin + sym_count > nsym, an odd
+ * d_out, unknown flags, no decode tables. sym_count 0: HZ_OK, nothing launched.
+ * Found on the device and reported by hz_ctx_sync, with nothing written for the
+ * block concerned: HZ_EINVAL for a block whose bytes and margins are not inside
+ * the slice; HZ_EFORMAT for a descending start[], for a block longer than its
+ * symbols times the longest code, for a block whose codewords do not end exactly
+ * at start[b + 1] (seek table) or whose first sub[] entry disagrees with start[b]
+ * (full index: the rest of sub[] is trusted as in hz_decode). Every walk is
+ * bounded by the block's symbol count and its end bit, and no load leaves
+ * [d_payload, d_payload + payload_bytes) rounded out to 64-byte lines below (base
+ * 0 only, as hz_decode) and to a 4-byte word above. */
+int hz_decode_range(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t payload_byte_base,
+                    const uint64_t *d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                    uint8_t *d_out, uint32_t flags);
+
+/* Expand a seek table into the complete block index of the stream (start[] copied,
+ * max_bits and sub[] computed, chains past the end as hz_pack writes them): byte for
+ * byte what hz_pack / hz_index_build write. d_payload is the whole payload;
+ * d_index holds hz_index_bytes(nsym); d_seek and d_index may be the same pointer.
+ * Stream-ordered, no scratch. A block that fails hz_decode_range's checks leaves
+ * its sub[] row unwritten and reports HZ_EFORMAT / HZ_EINVAL at hz_ctx_sync. */
+int hz_index_expand(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, const uint64_t *d_seek,
+                    uint64_t nsym, uint64_t *d_index);
+
 /* Decode the first nsym codewords of an index-less stream (a .compressed file
  * from the reference encoder; Decompressor.cu:259-291 decodes it serially) into
  * d_out (2*nsym bytes, 16-byte aligned) with no block index: a length walk of
@@ -337,6 +405,20 @@ int hz_extract_file(const char *path, char *out_name, size_t out_name_cap, int v
 int hz_encode_host(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
 int hz_encoded_size(const uint8_t *in, uint64_t n, uint64_t *out_len);
 int hz_decode_host(const uint8_t *file, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_n);
+
+/* Whole-buffer host forms of random access (device work inside). hz_seek_build_host:
+ * the seek table of a .compressed image (reference-written files included) into
+ * seek (cap_bytes >= hz_seek_bytes(*nsym), else HZ_ECAP with *nsym set); bits
+ * count from the file byte that holds the first payload bit (hz_header_info's
+ * payload_byte). hz_decode_range_host: bytes [offset, offset + count) of the
+ * original from an image and its host seek table into out; odd offsets and counts
+ * are served by decoding the covering symbols, and the odd trailing byte of an
+ * odd-sized original comes from the header. Only the header's codebook, the
+ * range's seek entries and the span's payload bytes go to the device.
+ * offset + count past the original's size: HZ_EINVAL. */
+int hz_seek_build_host(const uint8_t *file, uint64_t len, uint64_t *seek, uint64_t cap_bytes, uint64_t *nsym);
+int hz_decode_range_host(const uint8_t *file, uint64_t len, const uint64_t *seek, uint64_t offset,
+                         uint64_t count, uint8_t *out);
 
 #ifdef __cplusplus
 }
