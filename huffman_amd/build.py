@@ -5,6 +5,7 @@ Outputs (git-ignored, shipped to the GPU box with the tree):
   huffman_amd/bin/archive             drop-in for the reference `archive`
   huffman_amd/bin/extract             drop-in for the reference `extract`
 """
+import concurrent.futures
 import hashlib
 import os
 import subprocess
@@ -20,11 +21,23 @@ BUILD_ID = os.path.join(PKG, "lib", "BUILD_ID")  # hash of the sources the libra
 BIN = os.path.join(PKG, "bin")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
+MAX_BUILD_JOBS = 16
 
-LIB_SOURCES = ["hz_kernels.hip", "hz_codebook_gpu.hip", "hz_codebook.cpp", "hz_host.cpp"]
-HEADERS = [os.path.join(CSRC, "hz_internal.h"), os.path.join(INCLUDE, "huffman_amd.h")]
-CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", f"--offload-arch={ARCH}",
-          f"-I{INCLUDE}", f"-I{CSRC}"]
+
+def lib_sources(src_dir):
+    """The library's translation units: every hz_*.hip / hz_*.cpp of a source directory (names, sorted)."""
+    return sorted(f for f in os.listdir(src_dir) if f.startswith("hz_") and f.endswith((".hip", ".cpp")))
+
+
+def headers(src_dir, inc_dir):
+    """Every header a unit may include: *.h of the source directory and the public header (paths, sorted)."""
+    return sorted(os.path.join(src_dir, f) for f in os.listdir(src_dir) if f.endswith(".h")) + \
+        [os.path.join(inc_dir, "huffman_amd.h")]
+
+
+LIB_SOURCES = lib_sources(CSRC)
+HEADERS = headers(CSRC, INCLUDE)
+CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result", f"--offload-arch={ARCH}"]
 
 
 def _stale(target, deps):
@@ -45,46 +58,60 @@ def _run(cmd, verbose):
         sys.stderr.write(r.stdout + r.stderr)
 
 
-def source_id():
+def source_id(src_dir=CSRC, inc_dir=INCLUDE):
     """sha256 (16 hex digits) of every source and header the library is built from."""
     h = hashlib.sha256()
-    for path in [os.path.join(CSRC, f) for f in LIB_SOURCES] + HEADERS:
+    for path in [os.path.join(src_dir, f) for f in lib_sources(src_dir)] + headers(src_dir, inc_dir):
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
 
 
+def build_jobs(units):
+    """Compiler processes at once: one per unit, at most MAX_BUILD_JOBS, fewer when MAX_JOBS or
+    CMAKE_BUILD_PARALLEL_LEVEL asks for fewer (never sized from the machine's CPU count)."""
+    jobs = min(MAX_BUILD_JOBS, max(1, units))
+    for var in ("MAX_JOBS", "CMAKE_BUILD_PARALLEL_LEVEL"):
+        v = os.environ.get(var, "")
+        if v.isdigit() and int(v) > 0:
+            jobs = min(jobs, int(v))
+    return jobs
+
+
+def compile_library(src_dir, inc_dir, obj_dir, out, defines=(), force=False, verbose=False):
+    """Compile every unit of src_dir (concurrently) into obj_dir and link them into the shared library `out`.
+    Objects older than their source or any header are rebuilt, all of them with force."""
+    os.makedirs(obj_dir, exist_ok=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    deps = headers(src_dir, inc_dir)
+    flags = CFLAGS + [f"-I{inc_dir}", f"-I{src_dir}"] + list(defines)
+    cmds, objs = [], []
+    for src in lib_sources(src_dir):
+        path = os.path.join(src_dir, src)
+        obj = os.path.join(obj_dir, src + ".o")
+        objs.append(obj)
+        if force or _stale(obj, [path] + deps):
+            lang = ["-x", "hip"] if src.endswith(".hip") else []
+            cmds.append([HIPCC] + flags + lang + ["-c", path, "-o", obj])
+    if cmds:
+        with concurrent.futures.ThreadPoolExecutor(build_jobs(len(cmds))) as pool:
+            for f in [pool.submit(_run, c, verbose) for c in cmds]:
+                f.result()
+    if force or _stale(out, objs):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out] + objs, verbose)
+    return out
+
+
 def build_variant(name, defines, verbose=False):
     """An A/B build of the library with extra -D flags into huffman_amd/lib_<name>/
     (loaded with HZ_LIB_VARIANT=lib_<name>; tools/ab.sh)."""
-    obj_dir = os.path.join(PKG, "_build_" + name)
-    lib = os.path.join(PKG, "lib_" + name, "libhuffman_amd.so")
-    os.makedirs(obj_dir, exist_ok=True)
-    os.makedirs(os.path.dirname(lib), exist_ok=True)
-    objs = []
-    for src in LIB_SOURCES:
-        obj = os.path.join(obj_dir, src + ".o")
-        lang = ["-x", "hip"] if src.endswith(".hip") else []
-        _run([HIPCC] + CFLAGS + defines + lang + ["-c", os.path.join(CSRC, src), "-o", obj], verbose)
-        objs.append(obj)
-    _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + objs, verbose)
-    return lib
+    return compile_library(CSRC, INCLUDE, os.path.join(PKG, "_build_" + name),
+                           os.path.join(PKG, "lib_" + name, "libhuffman_amd.so"), defines, True, verbose)
 
 
 def build(verbose=False, force=False):
-    os.makedirs(OBJ, exist_ok=True)
-    os.makedirs(os.path.dirname(LIB), exist_ok=True)
     os.makedirs(BIN, exist_ok=True)
-    objs = []
-    for src in LIB_SOURCES:
-        path = os.path.join(CSRC, src)
-        obj = os.path.join(OBJ, src + ".o")
-        objs.append(obj)
-        if force or _stale(obj, [path] + HEADERS):
-            lang = ["-x", "hip"] if src.endswith(".hip") else []
-            _run([HIPCC] + CFLAGS + lang + ["-c", path, "-o", obj], verbose)
-    if force or _stale(LIB, objs):
-        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB] + objs, verbose)
+    compile_library(CSRC, INCLUDE, OBJ, LIB, (), force, verbose)
     sid = source_id()
     if not os.path.exists(BUILD_ID) or open(BUILD_ID).read().strip() != sid:
         with open(BUILD_ID, "w") as f:
@@ -93,8 +120,8 @@ def build(verbose=False, force=False):
         src = os.path.join(CSRC, f"cli_{name}.cpp")
         out = os.path.join(BIN, name)
         if force or _stale(out, [src, LIB] + HEADERS):
-            _run([HIPCC] + CFLAGS + [src, "-o", out, f"-L{os.path.dirname(LIB)}", "-lhuffman_amd",
-                                     "-Wl,-rpath,$ORIGIN/../lib"], verbose)
+            _run([HIPCC] + CFLAGS + [f"-I{INCLUDE}", f"-I{CSRC}", src, "-o", out, f"-L{os.path.dirname(LIB)}",
+                                     "-lhuffman_amd", "-Wl,-rpath,$ORIGIN/../lib"], verbose)
     return LIB
 
 

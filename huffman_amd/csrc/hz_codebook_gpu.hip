@@ -17,11 +17,9 @@
 #include <stdint.h>
 
 #include "huffman_amd.h"
-#include "hz_internal.h"
+#include "hz_device.h"
 
 namespace hz {
-
-#define HZ_DEV __device__ __forceinline__
 
 // ---- codebook -----------------------------------------------------------
 // 1. Sort: keys (count << 16 | symbol) in 64 tiles of 1024; an LSD radix sort

@@ -1,7 +1,7 @@
 // hz_host.cpp -- C ABI implementation: contexts, stage wrappers, and the
 // file-level `archive` / `extract` flow (Compressor.cu:315-632,
 // Decompressor.cu:47-114). Device work always runs through the gfx950 kernels
-// of hz_kernels.hip; there is no CPU fallback for any stage.
+// of the hz_*.hip files; there is no CPU fallback for any stage.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>

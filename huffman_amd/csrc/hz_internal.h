@@ -1,5 +1,6 @@
 // hz_internal.h -- shared layout constants and launch interfaces between the
-// host side (hz_host.cpp) and the gfx950 kernels (hz_kernels.hip).
+// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_kernels.hip,
+// hz_codebook_gpu.hip; DESIGN.md "Source layout").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -74,6 +75,28 @@ __host__ __device__ inline RangeGeom range_geom(uint64_t nsym) {
     g.off_start = g.off_dot + 8 * g.nranges;
     g.bytes = g.off_start + 8 * (g.nranges + 1);
     return g;
+}
+// The range buffer as the histogram (hz_hist.hip) and the pack (hz_pack.hip) kernels take it.
+struct RangeArgs {
+    uint32_t* snap;              // [nranges][32768] LDS images
+    uint32_t* list;              // [groups][1 + list_cap] carry records
+    unsigned long long* dot;     // [nranges]
+    unsigned long long* start;   // [nranges + 1]
+    uint64_t nsym, nblocks, bpr, nranges;
+    uint32_t groups, list_cap;
+    uint32_t* err;
+};
+
+inline RangeArgs range_args(void* buf, const RangeGeom& g, uint32_t* err) {
+    RangeArgs r;
+    uint8_t* b = reinterpret_cast<uint8_t*>(buf);
+    r.snap = reinterpret_cast<uint32_t*>(b);
+    r.list = reinterpret_cast<uint32_t*>(b + g.off_list);
+    r.dot = reinterpret_cast<unsigned long long*>(b + g.off_dot);
+    r.start = reinterpret_cast<unsigned long long*>(b + g.off_start);
+    r.nsym = g.nsym; r.nblocks = g.nblocks; r.bpr = g.bpr; r.nranges = g.nranges;
+    r.groups = g.groups; r.list_cap = g.list_cap; r.err = err;
+    return r;
 }
 
 // Histogram LDS word of symbol pair s >> 1. Byte-pair symbols of skewed data
@@ -223,7 +246,7 @@ __host__ __device__ inline uint32_t hot_slot(uint32_t s, uint32_t m) { return (s
 // (the first byte alone would pick the bank; skewed data keeps it small).
 __host__ __device__ inline uint32_t hot_word(uint32_t slot) { return slot ^ ((slot >> 8) & 0x3fu); }
 
-// Launchers (hz_kernels.hip). All stream ordered; return hipError_t.
+// Launchers (hz_hist.hip, hz_pack.hip, hz_kernels.hip). All stream ordered; return hipError_t.
 hipError_t launch_hist16(const uint8_t* d_in, uint64_t n, unsigned long long* d_hist, int ncu,
                          hipStream_t s);
 hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long long* d_hist, void* d_ranges,
