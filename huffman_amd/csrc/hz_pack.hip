@@ -938,7 +938,13 @@ __global__ __launch_bounds__(kPackThreads) void k_pack_fixed16(PackArgs a, uint6
             }
             a.index_sub[j] = sub;
             if (lane == 0) a.index[blk] = start_bit + (uint64_t)blk * kBlockSyms * 16;
-            if (j + 1 == nl) a.index[a.nblocks] = start_bit + 16 * a.nsym;
+            if (j + 1 == nl) {
+                a.index[a.nblocks] = start_bit + 16 * a.nsym;
+                // the last block's lanes past the stream's end run no iteration: their chains start at
+                // the end bit, as pack_block_emit / hz_index_build / hz_index_expand write them
+                const uint64_t e16 = (start_bit + 16 * a.nsym) & 0xffffu;
+                for (uint64_t q = nl; q < a.nblocks * kWave; ++q) a.index_sub[q] = e16 * 0x0001000100010001ull;
+            }
             if (j == 0) a.index[a.nblocks + 1] = 16ull * (a.nsym < (uint64_t)kBlockSyms ? a.nsym : (uint64_t)kBlockSyms);
         }
     }

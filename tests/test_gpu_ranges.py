@@ -57,6 +57,34 @@ def _fib_wide(n_target, seed):
     return torch.from_numpy(np.tile(base, reps).astype("<u2").view(np.uint8)).cuda()
 
 
+PAIR_A, PAIR_B = 0x1234, 0x1235  # the two halves of one LDS word of the histogram (hz_hist.hip hist_word)
+
+
+def _paired(n, seed):
+    """48 % of the symbols PAIR_A, 48 % PAIR_B, the rest over 300 symbols, in the lockstep vector
+    pattern (every 16-byte vector A,B,A,B,A,B,A,B before the rest is scattered in): both halves of
+    one LDS word cross 65 536 together in every range, so the high-half wrap, the low-half carry and
+    its undo (a negative carry record) all reach the plan."""
+    import torch
+    rng = np.random.default_rng(seed)
+    nsym = n // 2
+    sym = np.tile(np.array([PAIR_A, PAIR_B], dtype="<u2"), (nsym + 1) // 2)[:nsym]
+    rest = np.nonzero(rng.random(nsym, dtype=np.float32) < 0.04)[0]
+    sym[rest] = rng.integers(1000, 1300, rest.size)
+    return torch.from_numpy(sym.view(np.uint8)).cuda()
+
+
+def _bincount(x):
+    """np.bincount of the u16 symbols of a device byte tensor, on its host copy (in slices: bincount
+    widens its input to 8 bytes per symbol)."""
+    host = x.cpu().numpy()
+    sym = host[:2 * (host.size // 2)].view("<u2")
+    h = np.zeros(65536, dtype=np.uint64)
+    for i in range(0, sym.size, 1 << 25):
+        h += np.bincount(sym[i:i + (1 << 25)], minlength=65536).astype(np.uint64)
+    return h
+
+
 def _both(dev, x, start_bit, lead):
     """(hist, payload, index) by the three-pass encode and by the range plan."""
     import torch
@@ -100,16 +128,22 @@ def _both(dev, x, start_bit, lead):
     ("zipf", 768 * MIB + 4098, 32 * 7 + 13, 0),  # 3 ranges per histogram workgroup
     ("skewed", 256 * MIB + 4096 * 3 + 2, 0, 0),  # DENSE tables, counter wraps in every range
     ("wide", 300 * MIB, 3, 0x5),               # WIDE tables (codes > 25 bits)
+    ("paired", 256 * MIB + 2 * 4099, 9, 0x101),  # both halves of one histogram word wrap together
 ])
 def test_range_plan_equals_three_pass(dev, kind, n, start_bit, lead):
     import torch
-    x = {"zipf": lambda: _zipf(n, 9), "skewed": lambda: _skewed(n, 4), "wide": lambda: _fib_wide(n, 2)}[kind]()
+    x = {"zipf": lambda: _zipf(n, 9), "skewed": lambda: _skewed(n, 4), "wide": lambda: _fib_wide(n, 2),
+         "paired": lambda: _paired(n, 6)}[kind]()
     n = x.numel()
     ((h3, p3, i3, _, _), (hr, pr, ir, took, rb)), nb, cb = _both(dev, x, start_bit, lead)
     assert rb > 0
     assert took == 1, "the range plan did not run"
     assert np.array_equal(h3, hr)
     assert int(h3.sum()) == n // 2
+    want = _bincount(x)
+    assert np.array_equal(h3, want), np.nonzero(h3 != want)[0][:8]
+    if kind == "paired":
+        assert min(int(want[PAIR_A]), int(want[PAIR_B])) > 0.47 * (n // 2) and np.count_nonzero(want) == 302
     assert np.array_equal(p3, pr)
     assert np.array_equal(i3.view(np.uint8)[:nb], ir.view(np.uint8)[:nb])
     del x

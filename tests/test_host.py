@@ -205,3 +205,27 @@ int main(int argc, char** argv) {
 def test_integration_example_compiles_and_links(built_lib, tmp_path):
     exe = build_integration_example(tmp_path)
     assert os.access(exe, os.X_OK)
+
+
+def test_codebook_longer_than_maxlen_is_rejected(built_lib):
+    """Fibonacci counts: 57 of them give a 56-bit code (HZ_MAXLEN, accepted); 58 would need 57 bits:
+    HZ_ETOOLONG, as the oracle refuses them too."""
+    import huffman_amd
+
+    def fib_hist(k):
+        fib = [1, 1]
+        while len(fib) < k:
+            fib.append(fib[-1] + fib[-2])
+        h = np.zeros(65536, dtype=np.uint64)
+        h[(np.arange(k, dtype=np.uint32) * 257 + 3).astype(np.uint16)] = fib
+        return h
+
+    cb = huffman_amd.build_codebook(fib_hist(57))
+    assert cb.max_len == 56 and cb.min_len == 1
+    _, ln, _ = oracle_lib.codebook(fib_hist(57))
+    assert np.array_equal(huffman_amd.codebook_arrays(cb)[1], ln)
+    with pytest.raises(huffman_amd.HZError) as e:
+        huffman_amd.build_codebook(fib_hist(58))
+    assert e.value.status == -4  # HZ_ETOOLONG
+    with pytest.raises(RuntimeError):
+        oracle_lib.codebook(fib_hist(58))
