@@ -576,90 +576,119 @@ HZ_DEV void dec_wave_pipe(const A& a, const uint32_t* lds, uint32_t* stg, uint32
 // lookups are consumed after the other three pairs' LDS walks, so a gather
 // has three walks to land in instead of one. Half as many waves (two staging
 // slots each) hold the same LDS; blocks b, b + 1, then b + stride, ...
+// The two blocks run half a block out of phase: block X (slot 0) is at steps
+// 4-7 while block Y (slot 1) is at steps 0-3, then Y at 4-7 beside X's
+// successor at 0-3, so one quad is mid-block whenever the other drains,
+// stores and refills its slot. The wave's first block runs steps 0-3 alone;
+// after the last pair the successor in slot 0 is a duplicate that is dropped
+// mid-block.
 template <typename A>
 HZ_DEV void dec_wave_pipe2(const A& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
                            uint64_t stride, int lane) {
     constexpr int C = 2 * kChainsPerLane;
+    constexpr int H = kChainSyms / 2;
     static_assert(kChainsPerLane == 4, "four pairs of chains over two blocks");
+    static_assert(kChainSyms == 8 && kPfStep == H, "a block's prefetch issues at the top of its second half");
     const __amdgpu_buffer_rsrc_t l2r = lut_l2_rsrc(a.l2);
-    [[maybe_unused]] const uint32_t stg_bit = (uint32_t)(stg - lds) * 32u - 1u;  // LDS bit address of the slots, minus 1
-    PipeMeta mc[2], mn[2], mn2[2];
-    uint4 sc[2][kStageUnroll], sn[2][kStageUnroll];
+    PipeMeta mn[2], mn2;  // mn[j]: the block slot j takes next; mn2: the one after it, from prefetch to commit
+    uint4 sn[kStageUnroll];  // one block's prefetch is in flight at a time
+    uint32_t p1[C];
+    uint32_t pk[2][kSPT / 2];
+    PipeLane st[C];
+    uint32_t g[C];
+    // slot j takes the block of mn[j] (its chunks are in sn); mn[j] moves on to mn2
+    auto commit = [&](int j) {
+        uint64_t w0;
+        dec_stage_commit<true>(a, mn[j], slot >> 2, stg + j * slot, lane, sn, w0);
+        uint32_t off[kChainsPerLane];
+        dec_chain_offsets(mn[j].sub, mn[j].b0, mn[j].b1 - mn[j].b0, lane, off);
+        // m = (E - 1) * 32 + 31 - r for the slot's top word E and r = the chain's next bit - 1,
+        // relative to stream word w0; a step of L bits subtracts L
+        const uint32_t top = (uint32_t)(stg - lds) + (uint32_t)(j + 1) * slot - 1u;
+        const uint32_t base = top * 32u - (uint32_t)(mn[j].b0 + a.bit_adj - (w0 << 5));
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        dec_meta_load(a, b + j, lane, mc[j]);
-        dec_meta_load(a, b + stride + j, lane, mn[j]);
+        for (int c = 0; c < kChainsPerLane; ++c) p1[j * kChainsPerLane + c] = base - off[c];
+        mn[j] = mn2;
+    };
+    // the staging chunks of slot j's next block, the metadata of block `after` (the one behind it)
+    auto prefetch = [&](int j, uint64_t after) {
+        dec_stage_prefetch(a, mn[j], lane, sn);
+        dec_meta_load(a, after, lane, mn2);
+    };
+    auto finish = [&](int c, int q) {
+        // a leaf in LDS (bit 31) beats its gather's 0 (read past num_records); a link loses to its
+        // gathered leaf: one v_max; and the leaf's byte 3 is 0x80 | L, subtracted whole (128 bits
+        // more per step, which the window address takes back: dec_pipe_ldsn's adj). 12 % fewer VALU
+        // per block pair; k_decode 10.09 -> 9.97 ms, chain decode 11.30 -> 11.13 ms (A/B, 16 GiB Zipf)
+        const uint32_t ee = st[c].e > g[c] ? st[c].e : g[c];
+        p1[c] -= ee >> 24;
+        const int i = ((c % kChainsPerLane) * kChainSyms + q) >> 1;
+        // an even step keeps the whole entry; the odd step packs both symbols (leaf bytes 1-2) by one v_perm
+        if (q & 1) pk[c / kChainsPerLane][i] = __builtin_amdgcn_perm(ee, pk[c / kChainsPerLane][i], 0x06050201u);
+        else pk[c / kChainsPerLane][i] = ee;
+    };
+    // two quads (one per block): a quad's gathers land behind the other quad's walk
+    auto issue4 = [&](int c, int q) {
+        // issue priority over the quad's LDS walk and gathers (decode 9.96-9.99 -> 9.88-9.91 ms, A/B)
+        __builtin_amdgcn_s_setprio(2);
+        dec_pipe_ldsn<4>(a, lds, p1 + c, st + c, 16u * (uint32_t)q);  // q steps taken: 16 q bytes
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            g[c + t] = __builtin_amdgcn_raw_buffer_load_b32(l2r, st[c + t].gi, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+    };
+    auto finish4 = [&](int c, int q) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) finish(c + t, q);
+    };
+    // prologue: both slots filled, the first block through steps 0 .. H - 1 alone
+    if (b >= a.nblocks) return;
+    dec_meta_load(a, b, lane, mn[0]);
+    dec_meta_load(a, b + 1, lane, mn[1]);
+    prefetch(0, b + stride);
+    commit(0);
+    prefetch(1, b + 1 + stride);
+    commit(1);
+    __builtin_amdgcn_wave_barrier();  // LDS ops of one wave complete in order
+    issue4(0, 0);
+#pragma unroll
+    for (int q = 0; q < H; ++q) {
+        finish4(0, q);
+        issue4(0, q + 1);
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) dec_stage_prefetch(a, mc[j], lane, sc[j]);
     for (; b < a.nblocks; b += stride) {
-        uint32_t p1[C];
+        // X = block b (slot 0) at steps H .. 7 beside Y = block b + 1 (slot 1) at steps 0 .. H - 1
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            uint64_t w0;
-            dec_stage_commit<true>(a, mc[j], slot >> 2, stg + j * slot, lane, sc[j], w0);
-            uint32_t off[kChainsPerLane];
-            dec_chain_offsets(mc[j].sub, mc[j].b0, mc[j].b1 - mc[j].b0, lane, off);
-            // m = (E - 1) * 32 + 31 - r for the slot's top word E and r = the chain's next bit - 1,
-            // relative to stream word w0; a step of L bits subtracts L
-            const uint32_t top = (uint32_t)(stg - lds) + (uint32_t)(j + 1) * slot - 1u;
-            const uint32_t base = top * 32u - (uint32_t)(mc[j].b0 + a.bit_adj - (w0 << 5));
-#pragma unroll
-            for (int c = 0; c < kChainsPerLane; ++c) p1[j * kChainsPerLane + c] = base - off[c];
-        }
-        __builtin_amdgcn_wave_barrier();  // LDS ops of one wave complete in order
-        uint32_t pk[2][kSPT / 2];
-        PipeLane st[C];
-        uint32_t g[C];
-        auto finish = [&](int c, int q) {
-            // a leaf in LDS (bit 31) beats its gather's 0 (read past num_records); a link loses to its
-            // gathered leaf: one v_max; and the leaf's byte 3 is 0x80 | L, subtracted whole (128 bits
-            // more per step, which the window address takes back: dec_pipe_ldsn's adj). 12 % fewer VALU
-            // per block pair; k_decode 10.09 -> 9.97 ms, chain decode 11.30 -> 11.13 ms (A/B, 16 GiB Zipf)
-            const uint32_t ee = st[c].e > g[c] ? st[c].e : g[c];
-            p1[c] -= ee >> 24;
-            const int i = ((c % kChainsPerLane) * kChainSyms + q) >> 1;
-            // an even step keeps the whole entry; the odd step packs both symbols (leaf bytes 1-2) by one v_perm
-            if (q & 1) pk[c / kChainsPerLane][i] = __builtin_amdgcn_perm(ee, pk[c / kChainsPerLane][i], 0x06050201u);
-            else pk[c / kChainsPerLane][i] = ee;
-        };
-        // two quads (one per block): a quad's gathers land behind the other quad's walk
-        auto issue4 = [&](int c, int q) {
-            // issue priority over the quad's LDS walk and gathers (decode 9.96-9.99 -> 9.88-9.91 ms, A/B)
-            __builtin_amdgcn_s_setprio(2);
-            dec_pipe_ldsn<4>(a, lds, p1 + c, st + c, 16u * (uint32_t)q);  // q steps taken: 16 q bytes
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                g[c + t] = __builtin_amdgcn_raw_buffer_load_b32(l2r, st[c + t].gi, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-        };
-        issue4(0, 0);
-#pragma unroll
-        for (int q = 0; q < kChainSyms; ++q) {
-            issue4(4, q);
-            if (q == kPfStep) {  // the next two blocks' staging chunks, the metadata after them
-#pragma unroll
-                for (int j = 0; j < 2; ++j) dec_stage_prefetch(a, mn[j], lane, sn[j]);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) dec_meta_load(a, b + 2 * stride + j, lane, mn2[j]);
+        for (int t = 0; t < H; ++t) {
+            issue4(4, t);
+            if (t == 0) prefetch(0, b + 2 * stride);  // X's successor X', the metadata of the one after
+            finish4(0, H + t);
+            if (t + 1 < H) {
+                issue4(0, H + t + 1);
+            } else {
+                // X is done: its stores go out behind Y's gathers (stores and loads share vmcnt and
+                // complete in order), X' takes the slot after X's last window read
+                __builtin_amdgcn_wave_barrier();
+                dec_store(a, b, lane, pk[0]);
+                commit(0);
+                __builtin_amdgcn_wave_barrier();
+                issue4(0, 0);
             }
+            finish4(4, t);
+        }
+        // Y at steps H .. 7 beside X' at steps 0 .. H - 1 (a duplicate past the stream's end, never stored)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) finish(c, q);
-            if (q + 1 < kChainSyms) issue4(0, q + 1);
-#pragma unroll
-            for (int c = 4; c < 8; ++c) finish(c, q);
+        for (int t = 0; t < H; ++t) {
+            issue4(4, H + t);
+            if (t == 0) prefetch(1, b + 1 + 2 * stride);
+            finish4(0, t);
+            issue4(0, t + 1);
+            finish4(4, H + t);
         }
         __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            if (b + j < a.nblocks) dec_store(a, b + j, lane, pk[j]);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            mc[j] = mn[j];
-            mn[j] = mn2[j];
-#pragma unroll
-            for (int u = 0; u < kStageUnroll; ++u) sc[j][u] = sn[j][u];
-        }
+        if (b + 1 < a.nblocks) dec_store(a, b + 1, lane, pk[1]);
+        commit(1);
+        __builtin_amdgcn_wave_barrier();
     }
 }
 

@@ -97,6 +97,8 @@ struct PackIn {
     uint64_t bstart;
 };
 
+// PSYM false: no previous-block symbol (the range pack carries the previous block's last bits).
+template <bool PSYM = true>
 HZ_DEV void pack_prefetch(const PackArgs& a, uint64_t blk, int lane, PackIn& x) {
     const uint64_t sym0 = blk * kBlockSyms + (uint64_t)lane * kSPT;
     const uint64_t ls = sym0 + kSPT <= a.nsym ? sym0 : 0;
@@ -106,8 +108,11 @@ HZ_DEV void pack_prefetch(const PackArgs& a, uint64_t blk, int lane, PackIn& x) 
         const uint4 v = p[q];
         x.raw[4 * q] = v.x; x.raw[4 * q + 1] = v.y; x.raw[4 * q + 2] = v.z; x.raw[4 * q + 3] = v.w;
     }
-    const uint64_t ps = blk ? blk * kBlockSyms - 32 + (uint64_t)(lane & 31) : 0;
-    x.psym = *reinterpret_cast<const uint16_t*>(a.in + 2 * ps);
+    x.psym = 0;
+    if constexpr (PSYM) {
+        const uint64_t ps = blk ? blk * kBlockSyms - 32 + (uint64_t)(lane & 31) : 0;
+        x.psym = *reinterpret_cast<const uint16_t*>(a.in + 2 * ps);
+    }
     x.bstart = a.blk_start ? a.blk_start[blk] : 0;  // range pack: a running sum instead
 }
 
@@ -123,7 +128,8 @@ struct HotLook {
 // kernels). A slot's entry carries its owner's bit 15 as the tag in bit 31: hit <=> bit 31 of
 // entry ^ (s << 16) is 0. A miss is the slot's other symbol, whose entry the escape table holds at
 // the same byte offset, so the escape address is one AND. !FULL: symbols k >= nvalid read 0.
-template <bool FULL>
+// !XS: the lane's 32 symbols only, no 33rd lookup of xs.
+template <bool FULL, bool XS = true>
 HZ_DEV void hot_issue(const PackArgs& a, const uint32_t (&raw)[kSPT / 2], uint32_t xs, HotLook& h, int nvalid = kSPT) {
     const uint32_t m2 = a.hot_mask | (a.hot_mask << 16);
     uint32_t ad[kSPT];
@@ -154,7 +160,7 @@ HZ_DEV void hot_issue(const PackArgs& a, const uint32_t (&raw)[kSPT / 2], uint32
     }
     uint32_t xslot = xs ^ ((uint32_t)((int32_t)(xs << 16) >> 31) & a.hot_mask);
     xslot = hot_word(xslot & 0x7fffu) << 2;
-    h.xx = lds_at(xslot);
+    if constexpr (XS) h.xx = lds_at(xslot);
     const char* esc = reinterpret_cast<const char*>(a.esc);
 #pragma unroll
     for (int k = 0; k < kSPT; ++k) {
@@ -162,11 +168,14 @@ HZ_DEV void hot_issue(const PackArgs& a, const uint32_t (&raw)[kSPT / 2], uint32
         h.mk[k] = (uint32_t)((int32_t)(h.x[k] ^ tag) >> 31);
         h.v[k] = *reinterpret_cast<const uint32_t*>(esc + (ad[k] & h.mk[k]));
     }
-    h.xmk = (uint32_t)((int32_t)(h.xx ^ (xs << 16)) >> 31);
-    h.xv = *reinterpret_cast<const uint32_t*>(esc + (xslot & h.xmk));
+    if constexpr (XS) {
+        h.xmk = (uint32_t)((int32_t)(h.xx ^ (xs << 16)) >> 31);
+        h.xv = *reinterpret_cast<const uint32_t*>(esc + (xslot & h.xmk));
+    }
 }
 // the blend is a v_bfi the compiler cannot turn back into a select: written as `miss ? esc[s] : e`
 // the loads become 33 exec-masked branches (12.73-12.87 vs 12.61-12.67 ms at 16 GiB Zipf, round 3 A/B)
+template <bool XS = true>
 HZ_DEV void hot_finish(const HotLook& h, uint32_t (&e)[kSPT], uint32_t& xe) {
 #pragma unroll
     for (int k = 0; k < kSPT; ++k) {
@@ -174,9 +183,11 @@ HZ_DEV void hot_finish(const HotLook& h, uint32_t (&e)[kSPT], uint32_t& xe) {
         asm volatile("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(h.mk[k]), "v"(h.v[k]), "v"(h.x[k]));
         e[k] = r;
     }
-    uint32_t r;
-    asm volatile("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(h.xmk), "v"(h.xv), "v"(h.xx));
-    xe = r;
+    if constexpr (XS) {
+        uint32_t r;
+        asm volatile("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(h.xmk), "v"(h.xv), "v"(h.xx));
+        xe = r;
+    }
 }
 
 // (len, code) of the lane's 32 symbols in register format (len << SH | code),
@@ -454,12 +465,60 @@ HZ_DEV void pack_block_count(int lane, PackBlk<MODE>& b) {
     b.bits = readlane(sn, 63);
 }
 
+// The 32 bits before a block from pe, the entry of one of the previous block's last 32 symbols in
+// each of lanes 0..31 (each code >= 1 bit): a concatenation scan (associative; (0, 0) is its
+// identity, which is what DPP lanes without a source read) over the rows, then row 0 into row 1.
+template <int MODE>
+HZ_DEV uint32_t pack_tail_scan(typename PackEnt<MODE>::T pe) {
+    using T = typename PackEnt<MODE>::T;
+    constexpr T CMASK = (T(1) << PackEnt<MODE>::kShift) - 1;
+    uint32_t pn = ent_len<MODE>(pe);
+    uint32_t pt = (uint32_t)(pe & CMASK);  // low 32 bits of the code
+    auto step = [&](uint32_t on, uint32_t ot) {
+        pt = pn >= 32 ? pt : ((ot << pn) | pt);
+        pn += on;
+    };
+    step(dpp0<kDppRowShr1>(pn), dpp0<kDppRowShr1>(pt));
+    step(dpp0<kDppRowShr2>(pn), dpp0<kDppRowShr2>(pt));
+    step(dpp0<kDppRowShr4>(pn), dpp0<kDppRowShr4>(pt));
+    step(dpp0<kDppRowShr8>(pn), dpp0<kDppRowShr8>(pt));
+    step(dpp0<kDppRowBcast15, 0xa>(pn), dpp0<kDppRowBcast15, 0xa>(pt));
+    return readlane(pt, 31);
+}
+
+// The 32 bits before block `blk` of a HOT stream, looked up from the input: what a range's first
+// block needs (the blocks after it take them from the emit before, pack_block_emit's CARRY).
+HZ_DEV uint32_t hot_prev_tail(const PackArgs& a, uint64_t blk, int lane) {
+    if (blk == 0) return a.lead;
+    const uint32_t xs = *reinterpret_cast<const uint16_t*>(a.in + 2 * (blk * kBlockSyms - 32 + (uint64_t)(lane & 31)));
+    uint32_t xslot = xs ^ ((uint32_t)((int32_t)(xs << 16) >> 31) & a.hot_mask);
+    xslot = hot_word(xslot & 0x7fffu) << 2;
+    const uint32_t xx = lds_at(xslot);
+    const uint32_t xmk = (uint32_t)((int32_t)(xx ^ (xs << 16)) >> 31);  // a miss: the escape table's entry
+    const uint32_t xv = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(a.esc) + (xslot & xmk));
+    return pack_tail_scan<ENC_HOT>((xv & xmk) | (xx & ~xmk));
+}
+
+// The last 32 bits of a block from the entries of its last lane (32 codes of >= 1 bit), for the
+// block after one that was not emitted here.
+template <int MODE>
+HZ_DEV uint32_t pack_own_tail(const PackBlk<MODE>& b) {
+    static_assert(MODE != ENC_WIDE, "u32 entries");
+    uint32_t t = 0;
+#pragma unroll
+    for (int k = 0; k < kSPT; ++k) t = (t << ent_len<MODE>(b.e[k])) | (b.e[k] & ((1u << PackEnt<MODE>::kShift) - 1u));
+    return readlane(t, 63);
+}
+
 // Writes block `blk` starting at absolute bit `bstart`, plus its index entries. SLOT_ONLY: the caller
 // has checked that the block goes through the wave's LDS slot (not the last block, fits the slot), so
-// the direct path is not compiled in.
-template <int MODE, bool SLOT_ONLY = false>
+// the direct path is not compiled in. CARRY (with SLOT_ONLY): *tail holds the 32 bits before the
+// block (b.pe is not read) and returns the block's own last 32 bits -- the low word of lane 63's
+// accumulator, since every lane holds 32 codes of >= 1 bit.
+template <int MODE, bool SLOT_ONLY = false, bool CARRY = false>
 HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int lane, const PackBlk<MODE>& b,
-                            uint64_t bstart, uint64_t& max_bits, PackOut* defer = nullptr) {
+                            uint64_t bstart, uint64_t& max_bits, PackOut* defer = nullptr, uint32_t* tail = nullptr) {
+    static_assert(!CARRY || (SLOT_ONLY && MODE != ENC_WIDE), "the carried tail is the slot path's");
     using T = typename PackEnt<MODE>::T;
     constexpr int SH = PackEnt<MODE>::kShift;
     constexpr T CMASK = (T(1) << SH) - 1;
@@ -469,22 +528,8 @@ HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int
     // The 32 bits before the block: codes of the previous block's last 32
     // symbols (each code >= 1 bit), combined across lanes 0..31.
     uint32_t ptail = a.lead;
-    if (blk > 0) {
-        // Concatenation scan (associative; (0, 0) is its identity, which is what
-        // DPP lanes without a source read) over lanes 0..31: rows, then row 0 into row 1.
-        uint32_t pn = ent_len<MODE>(b.pe);
-        uint32_t pt = (uint32_t)(b.pe & CMASK);  // low 32 bits of the code
-        auto step = [&](uint32_t on, uint32_t ot) {
-            pt = pn >= 32 ? pt : ((ot << pn) | pt);
-            pn += on;
-        };
-        step(dpp0<kDppRowShr1>(pn), dpp0<kDppRowShr1>(pt));
-        step(dpp0<kDppRowShr2>(pn), dpp0<kDppRowShr2>(pt));
-        step(dpp0<kDppRowShr4>(pn), dpp0<kDppRowShr4>(pt));
-        step(dpp0<kDppRowShr8>(pn), dpp0<kDppRowShr8>(pt));
-        step(dpp0<kDppRowBcast15, 0xa>(pn), dpp0<kDppRowBcast15, 0xa>(pt));
-        ptail = readlane(pt, 31);
-    }
+    if constexpr (CARRY) ptail = *tail;
+    else if (blk > 0) ptail = pack_tail_scan<MODE>(b.pe);
     const uint64_t o = bstart + ex_n;
     // every word this block writes lies below ceil(bend / 32)
     const bool fits = ((bend + 31) >> 5) <= a.out_words;
@@ -508,6 +553,7 @@ HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int
         }
         const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)ptail, (int)(uint32_t)acc, kDppWaveShr1,
                                                                     0xf, 0xf, false);  // lane 0: ptail
+        if constexpr (CARRY) *tail = readlane((uint32_t)acc, 63);
         const uint32_t h = (uint32_t)(o & 31);
         if (h) sl[(uint32_t)((o >> 5) - wfirst)] |= prev << (32 - h);
         __builtin_amdgcn_wave_barrier();
@@ -653,6 +699,14 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
             nrun = r < a.nranges ? a.rstart[r] : 0;
             return n;
         };
+        // RNG: a wave packs the blocks of a range in order, so the 32 bits before a block are the
+        // last 32 bits of the emit before it (tail, valid when have_tail): no previous-block symbol,
+        // 33rd lookup, 33rd escape load or concatenation scan per block. A range's first block looks
+        // them up (hot_prev_tail); the block after a cold-listed one takes them from that block's
+        // last lane (pack_own_tail).
+        constexpr bool kCarry = RNG;
+        uint32_t tail = 0;
+        bool have_tail = false;
         bool nb_newr;
         uint64_t nb_run;
         uint64_t nb = next(blk, nb_newr, nb_run);
@@ -661,28 +715,28 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
         uint64_t bst_cur = run;
         if (blk < a.nblocks) {
             PackIn cur;
-            pack_prefetch(a, blk, lane, cur);
-            hot_issue<true>(a, cur.raw, cur.psym, hl);
+            pack_prefetch<!kCarry>(a, blk, lane, cur);
+            hot_issue<true, !kCarry>(a, cur.raw, cur.psym, hl);
             if (!RNG) bst_cur = cur.bstart;
-            pack_prefetch(a, nb < a.nblocks ? nb : blk, lane, nx);
+            pack_prefetch<!kCarry>(a, nb < a.nblocks ? nb : blk, lane, nx);
         }
         while (blk < a.nblocks) {
             bool nn_newr;
             uint64_t nn_run;
             const uint64_t nnb = next(nb, nn_newr, nn_run);
             PackBlk<MODE> b;
-            hot_finish(hl, b.e, b.pe);
+            hot_finish<!kCarry>(hl, b.e, b.pe);
             b.nvalid = kSPT;
             // issue priority while the lookups and escape loads go out (the SIMD's other wave computes):
             // pack 8.31-8.33 -> 8.23-8.26 ms, A/B
             __builtin_amdgcn_s_setprio(2);
-            hot_issue<true>(a, nx.raw, nx.psym, hl);  // block k+1 (past the wave's end: a repeat, unused)
+            hot_issue<true, !kCarry>(a, nx.raw, nx.psym, hl);  // block k+1 (past the wave's end: a repeat, unused)
             __builtin_amdgcn_s_setprio(0);
             const uint64_t nbst = nx.bstart;
             pack_copyout(a, slot, lane, po);  // block k-1's stores, behind the escape loads
             po.pending = false;
             const uint64_t pb = nnb < a.nblocks ? nnb : (nb < a.nblocks ? nb : blk);
-            pack_prefetch(a, pb, lane, nx);
+            pack_prefetch<!kCarry>(a, pb, lane, nx);
             pack_block_count<MODE>(lane, b);
             const uint64_t bst = bst_cur;
             const uint64_t wfirst = bst >> 5;
@@ -693,9 +747,14 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
                     a.cold[1 + 2 * i] = blk;
                     a.cold[2 + 2 * i] = bst;
                 }
+                if constexpr (kCarry) tail = pack_own_tail<MODE>(b);
+            } else if constexpr (kCarry) {
+                if (!have_tail) tail = hot_prev_tail(a, blk, lane);  // the first block of a range
+                pack_block_emit<MODE, true, true>(a, slot, blk, lane, b, bst, max_bits, &po, &tail);
             } else {
                 pack_block_emit<MODE, true>(a, slot, blk, lane, b, bst, max_bits, &po);
             }
+            have_tail = !nb_newr;
             if (RNG) run = nb_newr ? nb_run : run + b.bits;
             bst_cur = RNG ? run : nbst;
             blk = nb;
