@@ -99,6 +99,7 @@ PROTOTYPES = [
     ("hz_pack_ranges", _I, [_P, _P, _U64, _U64, _U32, _P, _U64, _P, _P]),
     ("hz_last_pack_ranges", _I, [_P]),
     ("hz_decode", _I, [_P, _P, _U64, _U64, _P, _P]),
+    ("hz_last_decode_chunks", _I, [_P]),
     ("hz_index_build", _I, [_P, _P, _U64, _U64, _U64, _P]),
     ("hz_seek_bytes", _U64, [_U64]),
     ("hz_seek_span", _I, [_P, _U64, _U64, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),

@@ -258,6 +258,10 @@ class Device:
     def decode(self, d_payload, payload_bytes, nsym, d_index, d_out):
         check(self.lib.hz_decode(self.h, d_payload, payload_bytes, nsym, d_index, d_out), "hz_decode")
 
+    def last_decode_chunks(self):
+        """Staging chunks per block the last decode prefetched (3 or 4; 0: a decoder without the choice)."""
+        return self.lib.hz_last_decode_chunks(self.h)
+
     def index_build(self, d_payload, payload_bytes, start_bit, nsym, d_index):
         check(self.lib.hz_index_build(self.h, d_payload, payload_bytes, start_bit, nsym, d_index), "hz_index_build")
 

@@ -99,6 +99,7 @@ struct hz_ctx {
            cap_dec_l2 = 0, cap_walk_lds = 0, cap_walk_esc = 0, cap_walk8 = 0, cap_chain_lds = 0, cap_chain_l2 = 0,
            cap_chain_esc = 0;
     int last_pack_ranges = 0;       // the last hz_pack_ranges call took the range plan
+    int last_decode_chunks = 0;     // staging chunks per block of the last hz_decode (launch_decode)
     // a FIXED16 part of hz_indexless_scan (every code 16 bits: positions are arithmetic, no chains)
     struct {
         bool on = false;
@@ -569,11 +570,13 @@ extern "C" int hz_decode(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_b
     HZ_TRY(hipSetDevice(c->device));
     HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 0));
     HZ_TRY(launch_decode(c->t, d_payload, payload_bytes, nsym, reinterpret_cast<const unsigned long long*>(d_index),
-                         d_out, c->d_err, c->ncu, c->stream));
+                         d_out, c->d_err, c->ncu, c->stream, 0, &c->last_decode_chunks));
     HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 1));
     c->ev_used[HZ_STAGE_DECODE] = true;
     return arm_err_check(c);
 }
+
+extern "C" int hz_last_decode_chunks(hz_ctx* c) { return c ? c->last_decode_chunks : 0; }
 
 extern "C" int hz_index_build(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
                               uint64_t nsym, uint64_t* d_index) {

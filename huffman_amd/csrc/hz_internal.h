@@ -261,7 +261,8 @@ uint64_t pack_scratch_words(uint64_t nsym);  // u64 words of d_scratch hz_pack n
 hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                          uint64_t nsym, const unsigned long long* d_index, uint8_t* d_out,
                          uint32_t* d_err, int ncu, hipStream_t s,
-                         uint64_t start0 = 0);  // d_index null (FIXED16 only): symbol i at start0 + 16 i
+                         uint64_t start0 = 0,  // d_index null (FIXED16 only): symbol i at start0 + 16 i
+                         int* stage_chunks = nullptr);  // out: staging chunks prefetched per block (0: no such choice)
 // Random access (DESIGN.md "Random access"). d_seek: the stream's start[] (a full index when full_index);
 // d_payload holds the stream's payload bytes [base, base + payload_bytes); d_scratch: range_scratch_words().
 constexpr uint64_t kRangeLeadBytes = HZ_RANGE_LEAD_BYTES, kRangeTailBytes = HZ_RANGE_TAIL_BYTES;

@@ -451,14 +451,15 @@ HZ_DEV void dec_meta_load(const DecArgs& a, uint64_t b, int lane, PipeMeta& m) {
     m.sub = dec_sub_load(a, bb, lane);
 }
 
-// The first kStageUnroll 16-byte chunks of a block's staging window, always
-// exactly kStageUnroll loads per lane (static vmcnt for the pipelined waits):
+// The first NS 16-byte chunks of a block's staging window, always
+// exactly NS loads per lane (static vmcnt for the pipelined waits):
 // chunks past the window or the payload read a clamped address and are fixed
 // up in registers. Requires nwords >= 4 (host check).
-HZ_DEV void dec_stage_prefetch(const DecArgs& a, const PipeMeta& m, int lane, uint4 (&v)[kStageUnroll]) {
+template <int NS>
+HZ_DEV void dec_stage_prefetch(const DecArgs& a, const PipeMeta& m, int lane, uint4 (&v)[NS]) {
     const uint64_t w0 = (((m.b0 + a.bit_adj) >> 5) & ~3ull) - 4;
 #pragma unroll
-    for (int u = 0; u < kStageUnroll; ++u) {
+    for (int u = 0; u < NS; ++u) {
         const uint64_t w = w0 + 4ull * ((uint32_t)lane + (uint32_t)u * kWave);
         const bool in = w < a.nwords;  // also false for a window that wrapped below word 0
         const uint64_t wl = !in ? 0 : (w + 4 <= a.nwords ? w : a.nwords - 4);
@@ -466,19 +467,19 @@ HZ_DEV void dec_stage_prefetch(const DecArgs& a, const PipeMeta& m, int lane, ui
     }
 }
 
-// Writes the prefetched chunks (fixed up for the payload's end) and any
-// further chunks of an oversized window into the slot.
+// Writes the NS prefetched chunks (fixed up for the payload's end) and any
+// further chunks of a longer window into the slot, loaded here (correct for any NS >= 1).
 // DESC: the slot holds the words in descending order (stream word t at slot word 4 npc_max - 1 - t).
-template <bool DESC = false>
+template <bool DESC = false, int NS>
 HZ_DEV void dec_stage_commit(const DecArgs& a, const PipeMeta& m, uint32_t npc_max, uint32_t* stg, int lane,
-                             const uint4 (&v)[kStageUnroll], uint64_t& w0) {
+                             const uint4 (&v)[NS], uint64_t& w0) {
     const uint64_t b0 = m.b0 + a.bit_adj, b1 = m.b1 + a.bit_adj;
     w0 = ((b0 >> 5) & ~3ull) - 4;
     const uint64_t wend = (b1 >> 5) + 2;
     uint32_t npc = (uint32_t)((wend - w0 + 3) >> 2);
     npc = npc < npc_max ? npc : npc_max;
 #pragma unroll
-    for (int u = 0; u < kStageUnroll; ++u) {
+    for (int u = 0; u < NS; ++u) {
         const uint32_t p = (uint32_t)lane + (uint32_t)u * kWave;
         if (p < npc) {
             const uint64_t w = w0 + 4ull * p;
@@ -499,7 +500,7 @@ HZ_DEV void dec_stage_commit(const DecArgs& a, const PipeMeta& m, uint32_t npc_m
                 reinterpret_cast<uint4*>(stg)[p] = make_uint4(bswap32(x.x), bswap32(x.y), bswap32(x.z), bswap32(x.w));
         }
     }
-    for (uint32_t p = (uint32_t)lane + kStageUnroll * kWave; p < npc; p += kWave) {  // oversized block: rare
+    for (uint32_t p = (uint32_t)lane + NS * kWave; p < npc; p += kWave) {  // oversized block: rare
         const uint4 x = dec_stage_load(a, w0 + 4ull * p);
         if (DESC)
             reinterpret_cast<uint4*>(stg)[npc_max - 1 - p] = make_uint4(bswap32(x.w), bswap32(x.z), bswap32(x.y), bswap32(x.x));
@@ -582,7 +583,9 @@ HZ_DEV void dec_wave_pipe(const A& a, const uint32_t* lds, uint32_t* stg, uint32
 // stores and refills its slot. The wave's first block runs steps 0-3 alone;
 // after the last pair the successor in slot 0 is a duplicate that is dropped
 // mid-block.
-template <typename A>
+// NS: staging chunks prefetched per block (kStageUnroll, or 3 where the launcher knows the mean block
+// fits them: dec_stage_chunks).
+template <int NS, typename A>
 HZ_DEV void dec_wave_pipe2(const A& a, const uint32_t* lds, uint32_t* stg, uint32_t slot, uint64_t b,
                            uint64_t stride, int lane) {
     constexpr int C = 2 * kChainsPerLane;
@@ -591,7 +594,7 @@ HZ_DEV void dec_wave_pipe2(const A& a, const uint32_t* lds, uint32_t* stg, uint3
     static_assert(kChainSyms == 8 && kPfStep == H, "a block's prefetch issues at the top of its second half");
     const __amdgpu_buffer_rsrc_t l2r = lut_l2_rsrc(a.l2);
     PipeMeta mn[2], mn2;  // mn[j]: the block slot j takes next; mn2: the one after it, from prefetch to commit
-    uint4 sn[kStageUnroll];  // one block's prefetch is in flight at a time
+    uint4 sn[NS];  // one block's prefetch is in flight at a time
     uint32_t p1[C];
     uint32_t pk[2][kSPT / 2];
     PipeLane st[C];
@@ -694,7 +697,8 @@ HZ_DEV void dec_wave_pipe2(const A& a, const uint32_t* lds, uint32_t* stg, uint3
 
 constexpr int kDecPipe2Threads = 512;  // two staging slots per wave (1024 with smaller hot heads: 15.2 ms vs 13.1)
 // PIPE: 0 plain block loop, 1 pipelined (one block per wave), 2 pipelined, two blocks per wave
-template <int MODE, bool WIDE, int PIPE>
+// NS: dec_wave_pipe2's staging chunks per block (PIPE 2 only)
+template <int MODE, bool WIDE, int PIPE, int NS = kStageUnroll>
 __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     copy_lds_table(lds, a.lds_img, a.lds_words);
@@ -709,7 +713,7 @@ __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode(
         if (nw2 > 0) {  // else one block per wave below (a stream whose largest block needs more)
             if (wid >= nw2) return;
             const uint64_t b = 2 * ((uint64_t)blockIdx.x * nw2 + wid), stride = 2 * (uint64_t)gridDim.x * nw2;
-            dec_wave_pipe2(a, lds, lds + a.lds_words + wid * 2 * slot, slot, b, stride, lane);
+            dec_wave_pipe2<NS>(a, lds, lds + a.lds_words + wid * 2 * slot, slot, b, stride, lane);
             return;
         }
     }
@@ -864,10 +868,11 @@ struct RangeDecArgs : DecArgs {
 
 // dec_stage_prefetch for a moved view: chunks outside the payload read the view's first real chunk
 // (dec_stage_commit zero-fills them as it does for the plain view's word 0).
-HZ_DEV void dec_stage_prefetch(const RangeDecArgs& a, const PipeMeta& m, int lane, uint4 (&v)[kStageUnroll]) {
+template <int NS>
+HZ_DEV void dec_stage_prefetch(const RangeDecArgs& a, const PipeMeta& m, int lane, uint4 (&v)[NS]) {
     const uint64_t w0 = (((m.b0 + a.bit_adj) >> 5) & ~3ull) - 4;
 #pragma unroll
-    for (int u = 0; u < kStageUnroll; ++u) {
+    for (int u = 0; u < NS; ++u) {
         const uint64_t w = w0 + 4ull * ((uint32_t)lane + (uint32_t)u * kWave);
         const bool in = w < a.nwords && w >= a.w_first;
         const uint64_t wl = !in ? a.w_first : (w + 4 <= a.nwords ? w : a.nwords - 4);
@@ -902,7 +907,7 @@ HZ_DEV void dec_store(const RangeDecArgs& a, uint64_t b, int lane, const uint32_
 
 // k_decode over the moved view: the same body (as one force-inlined function templated on the argument
 // type it compiles to other instructions in all ten instances, so it is kept twice).
-template <int MODE, bool WIDE, int PIPE>
+template <int MODE, bool WIDE, int PIPE, int NS = kStageUnroll>
 __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode_range(RangeDecArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     copy_lds_table(lds, a.lds_img, a.lds_words);
@@ -917,7 +922,7 @@ __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode_
         if (nw2 > 0) {  // else one block per wave below (a stream whose largest block needs more)
             if (wid >= nw2) return;
             const uint64_t b = 2 * ((uint64_t)blockIdx.x * nw2 + wid), stride = 2 * (uint64_t)gridDim.x * nw2;
-            dec_wave_pipe2(a, lds, lds + a.lds_words + wid * 2 * slot, slot, b, stride, lane);
+            dec_wave_pipe2<NS>(a, lds, lds + a.lds_words + wid * 2 * slot, slot, b, stride, lane);
             return;
         }
     }
@@ -938,15 +943,28 @@ __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode_
 // index's max_bits and idles the waves that do not get one. Up to two
 // workgroups per CU (each holds its own table copy): whichever shape runs
 // more waves.
-template <int MODE, bool WIDE, int PIPE, typename A>
+template <int MODE, bool WIDE, int PIPE, int NS, typename A>
 static const void* decode_fn() {
-    if constexpr (std::is_same<A, DecArgs>::value) return (const void*)k_decode<MODE, WIDE, PIPE>;
-    else return (const void*)k_decode_range<MODE, WIDE, PIPE>;
+    if constexpr (std::is_same<A, DecArgs>::value) return (const void*)k_decode<MODE, WIDE, PIPE, NS>;
+    else return (const void*)k_decode_range<MODE, WIDE, PIPE, NS>;
 }
 
-template <int MODE, bool WIDE, int PIPE, typename A = DecArgs>
+// Staging chunks the two-blocks-per-wave decoder prefetches per block: 3 where three chunks (3 KiB)
+// hold the mean block's window, else kStageUnroll. From the view's size alone (no device read):
+// nwords * 4 / nblocks bounds the mean block's bytes; the window adds the 16-byte pad before the block
+// and the two words read past its last bit; the slack (1/64 of the mean + 16 bytes) covers the first
+// word's offset in its chunk (up to 12 bytes) and the spread of the block sizes about their mean (a
+// block is 2048 codes: at a code-length deviation of 8 bits, 8 sqrt(2048) = 362 bits = 45 bytes, 1/64
+// of 3 KiB). Any choice decodes any stream: a longer window's further chunks are loaded at the commit.
+constexpr int kStageFew = 3;
+static int dec_stage_chunks(uint64_t nwords, uint64_t nblocks) {
+    const uint64_t mean = (nwords * 4 + nblocks - 1) / nblocks;
+    return mean + 16 + 8 + mean / 64 + 16 < 16ull * kWave * kStageFew ? kStageFew : kStageUnroll;
+}
+
+template <int MODE, bool WIDE, int PIPE, typename A = DecArgs, int NS = kStageUnroll>
 static hipError_t run_decode(const A& a, uint64_t payload_bits, int ncu, hipStream_t s) {
-    const void* fn = decode_fn<MODE, WIDE, PIPE, A>();
+    const void* fn = decode_fn<MODE, WIDE, PIPE, NS, A>();
     {
         hipError_t e = ensure_lds_limit(fn, kLdsBytes);
         if (e != hipSuccess) return e;
@@ -993,22 +1011,29 @@ static int dec_pipe_mode() {
 
 // The block decoder of a codebook. pipe_ok: the caller's view holds the four words the pipelined
 // decoders' staging prefetch needs; payload_bits: see run_decode.
+// *stage_chunks (nullable): the staging chunks prefetched per block, 0 for a decoder without that choice.
 template <typename A>
 static hipError_t decode_dispatch(const Tables& t, const A& a, bool pipe_ok, uint64_t payload_bits, int ncu,
-                                  hipStream_t s) {
+                                  hipStream_t s, int* stage_chunks = nullptr) {
+    if (stage_chunks) *stage_chunks = 0;
     if (t.dec_mode == DEC_DENSE) return run_decode<DEC_DENSE, false, 0>(a, payload_bits, ncu, s);
     if (t.dec_max_len > 32) return run_decode<DEC_LUT, true, 0>(a, payload_bits, ncu, s);
     // two levels suffice (no lookup chain past a global subtable): pipelined gathers
     const int pipe_env = dec_pipe_mode();
-    if (pipe_env && t.dec_max_len <= t.dec_k + t.dec_level_bits && pipe_ok)
-        return pipe_env == 1 ? run_decode<DEC_LUT, false, 1>(a, payload_bits, ncu, s)
-                             : run_decode<DEC_LUT, false, 2>(a, payload_bits, ncu, s);
+    if (pipe_env && t.dec_max_len <= t.dec_k + t.dec_level_bits && pipe_ok) {
+        if (pipe_env == 1) return run_decode<DEC_LUT, false, 1>(a, payload_bits, ncu, s);
+        const int ns = dec_stage_chunks(a.nwords, a.nblocks);
+        if (stage_chunks) *stage_chunks = ns;
+        return ns == kStageFew ? run_decode<DEC_LUT, false, 2, A, kStageFew>(a, payload_bits, ncu, s)
+                               : run_decode<DEC_LUT, false, 2>(a, payload_bits, ncu, s);
+    }
     return run_decode<DEC_LUT, false, 0>(a, payload_bits, ncu, s);
 }
 
 hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t nsym,
                          const unsigned long long* d_index, uint8_t* d_out, uint32_t* d_err, int ncu,
-                         hipStream_t s, uint64_t start0) {
+                         hipStream_t s, uint64_t start0, int* stage_chunks) {
+    if (stage_chunks) *stage_chunks = 0;
     if (nsym == 0) return hipSuccess;
     if (!d_index && t.dec_mode != DEC_FIXED16) return hipErrorInvalidValue;
     DecArgs a;
@@ -1034,7 +1059,7 @@ hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t pay
         hipLaunchKernelGGL(k_decode_fixed16, dim3(wgs), dim3(1024), kFixed16LdsBytes, s, a, nb);
         return hipGetLastError();
     }
-    return decode_dispatch(t, a, a.nwords >= 4, payload_bytes * 8, ncu, s);
+    return decode_dispatch(t, a, a.nwords >= 4, payload_bytes * 8, ncu, s, stage_chunks);
 }
 
 // ===========================================================================

@@ -211,6 +211,10 @@ int hz_last_pack_ranges(hz_ctx *ctx);
  * Replaces translateFile (Decompressor.cu:259-291). */
 int hz_decode(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t nsym,
               const uint64_t *d_index, uint8_t *d_out);
+/* Diagnostic: 16-byte staging chunks per lane the last hz_decode prefetched for
+ * every block (3 where the payload's mean block fits 3 KiB, else 4), 0 when its
+ * decoder has no such choice. The decoded bytes do not depend on it. */
+int hz_last_decode_chunks(hz_ctx *ctx);
 
 /* Build the block index of an index-less stream (a .compressed file from
  * the reference encoder) on the device. If the payload holds fewer than nsym
