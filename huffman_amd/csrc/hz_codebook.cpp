@@ -593,7 +593,7 @@ int build_dec_lut(const hz_codebook* cb, std::vector<uint32_t>& img, std::vector
     return HZ_OK;
 }
 
-// Index walker tables (hz_kernels.hip k_idx_walk): a walk needs code LENGTHS
+// Index walker tables (hz_index.hip k_idx_walk): a walk needs code LENGTHS
 // only. img: one nibble per K-bit window (window w in byte w / 2, the high
 // nibble for odd w), K = max(2, min(max_len, kWalkK, min_len + 14)): the length
 // of the code the window starts with, minus bias = min_len - 1; for a window that
@@ -645,7 +645,7 @@ void build_walk_len(const hz_codebook* cb, std::vector<uint32_t>& img, std::vect
 
 }  // namespace hz
 
-// The chain walker's length table (hz_kernels.hip k_chain_walk): one BYTE per K-bit window, K =
+// The chain walker's length table (hz_chain.hip k_chain_walk): one BYTE per K-bit window, K =
 // min(max_len, 16) (2^16 bytes, the same 64 KiB of LDS as the 17-bit nibble table): the length of the
 // code the window starts with when that code is at most K bits, or when every code under the
 // window's prefix has one length; 0 (escape: the walker reads esc, build_walk_len's 2^max_len table)

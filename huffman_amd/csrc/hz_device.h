@@ -1,5 +1,7 @@
 // hz_device.h -- what every gfx950 translation unit shares: wave and LDS helpers (force-inlined
-// device functions; no relocatable device code) and the launch helpers that cross units.
+// device functions; no relocatable device code) and the launch helpers that cross units (defined in
+// hz_pack.hip, as is stage_scatter, hz_internal.h). What only the decode side shares: hz_decode_device.h,
+// hz_walk_device.h.
 #pragma once
 #include "hz_internal.h"
 

@@ -1,6 +1,6 @@
 // hz_internal.h -- shared layout constants and launch interfaces between the
-// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_kernels.hip,
-// hz_codebook_gpu.hip; DESIGN.md "Source layout").
+// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_decode.hip,
+// hz_index.hip, hz_chain.hip, hz_codebook_gpu.hip; DESIGN.md "Source layout").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -246,11 +246,15 @@ __host__ __device__ inline uint32_t hot_slot(uint32_t s, uint32_t m) { return (s
 // (the first byte alone would pick the bank; skewed data keeps it small).
 __host__ __device__ inline uint32_t hot_word(uint32_t slot) { return slot ^ ((slot >> 8) & 0x3fu); }
 
-// Launchers (hz_hist.hip, hz_pack.hip, hz_kernels.hip). All stream ordered; return hipError_t.
+// Launchers, by the file that defines them. All stream ordered; return hipError_t.
+// ---- hz_hist.hip ------------------------------------------------------------
+hipError_t launch_generate(uint8_t* d_out, uint64_t n, uint64_t offset, int kind, uint64_t seed,
+                           const unsigned long long* d_thr, hipStream_t s);
 hipError_t launch_hist16(const uint8_t* d_in, uint64_t n, unsigned long long* d_hist, int ncu,
                          hipStream_t s);
 hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long long* d_hist, void* d_ranges,
                                 uint32_t* d_err, hipStream_t s);  // range plan (RangeGeom)
+// ---- hz_pack.hip (and ensure_lds_limit, launch_scan: hz_device.h) -------------
 // d_ranges (nullable): the range plan of d_in from launch_hist16_ranges; *used_ranges = 1 when the
 // pack took it (else count + scan + write)
 hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint64_t start_bit,
@@ -258,6 +262,15 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
                        unsigned long long* d_index, uint32_t* d_err, int ncu, hipStream_t s,
                        void* d_ranges = nullptr, int* used_ranges = nullptr);
 uint64_t pack_scratch_words(uint64_t nsym);  // u64 words of d_scratch hz_pack needs
+// Table uploads: segments of a pinned host staging buffer copied to their device tables by one kernel
+// (it reads the host memory over PCIe: one launch per upload instead of one copy per table).
+struct StageSeg {
+    void* dst;
+    uint64_t off, bytes;  // off: 16-byte aligned in the staging buffer; bytes: a multiple of 4
+};
+constexpr int kStageMaxSegs = 16;
+hipError_t stage_scatter(const uint8_t* h_src, const StageSeg* segs, int nseg, hipStream_t s);
+// ---- hz_decode.hip ----------------------------------------------------------
 hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                          uint64_t nsym, const unsigned long long* d_index, uint8_t* d_out,
                          uint32_t* d_err, int ncu, hipStream_t s,
@@ -274,12 +287,14 @@ hipError_t launch_decode_range(const Tables& t, const uint8_t* d_payload, uint64
 hipError_t launch_index_expand(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                                const unsigned long long* d_seek, uint64_t nsym, unsigned long long* d_index,
                                uint32_t* d_err, hipStream_t s);
+// ---- hz_index.hip -----------------------------------------------------------
 hipError_t launch_index_build(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                               uint64_t start_bit, uint64_t nsym, unsigned long long* d_index,
                               unsigned long long* d_scratch, uint32_t* d_err, uint32_t* h_scratch, int ncu,
                               hipStream_t s);  // synchronises the stream (iterates to a fixed point)
 uint64_t index_scratch_words(uint64_t payload_bytes, uint64_t start_bit);  // u64 words hz_index_build needs
-// Index-less decode in chain blocks (hz_kernels.hip; no block index, stream-ordered: no host
+// ---- hz_chain.hip -----------------------------------------------------------
+// Index-less decode in chain blocks (no block index, stream-ordered: no host
 // synchronisation). Phases over a PART of the payload (bits [part_begin, part_end) after start_bit; the
 // whole payload for one device, a slice per rank for one stream split over ranks):
 //   chain_scan   : walk, fix-ups, scans, block descriptors; summary in chain_info (device u64):
@@ -308,22 +323,13 @@ const unsigned long long* chain_info(const ChainState* st);
 void chain_invalidate(ChainState* st);  // the scratch or tables it points into changed
 hipError_t chain_summary(const ChainState* st, unsigned long long* d_dst, hipStream_t s);  // 3 x u64, stream bits
 hipError_t put3(unsigned long long* d_dst, uint64_t a, uint64_t b, uint64_t c, hipStream_t s);  // stream-ordered
-// Table uploads: segments of a pinned host staging buffer copied to their device tables by one kernel
-// (it reads the host memory over PCIe: one launch per upload instead of one copy per table).
-struct StageSeg {
-    void* dst;
-    uint64_t off, bytes;  // off: 16-byte aligned in the staging buffer; bytes: a multiple of 4
-};
-constexpr int kStageMaxSegs = 16;
-hipError_t stage_scatter(const uint8_t* h_src, const StageSeg* segs, int nseg, hipStream_t s);
+// ---- hz_codebook_gpu.hip ----------------------------------------------------
 hipError_t launch_codebook(const unsigned long long* d_hist, hz_codebook* d_cb, unsigned long long* d_ws,
-                           uint32_t* d_err, hipStream_t s);  // hz_codebook_gpu.hip
+                           uint32_t* d_err, hipStream_t s);
 uint64_t codebook_ws_words();
 hipError_t launch_header_write(const hz_codebook* d_cb, uint64_t n, uint32_t last_byte, uint8_t* d_out, uint64_t cap,
                                unsigned long long* d_info, unsigned long long* d_ws, uint32_t* d_err, hipStream_t s);
 hipError_t launch_header_parse(const uint8_t* d_file, uint64_t len, hz_codebook* d_cb, unsigned long long* d_info,
                                unsigned long long* d_ws, uint32_t* d_err, hipStream_t s);
-hipError_t launch_generate(uint8_t* d_out, uint64_t n, uint64_t offset, int kind, uint64_t seed,
-                           const unsigned long long* d_thr, hipStream_t s);
 
 }  // namespace hz

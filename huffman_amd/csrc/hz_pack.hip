@@ -1,4 +1,5 @@
-// hz_pack.hip -- the pack, its range plan and the u64 scan every stage shares.
+// hz_pack.hip -- the pack, its range plan, and the launch helpers no one stage owns: the u64 scan every
+// stage shares, ensure_lds_limit and the table upload (stage_scatter).
 //
 //   k_pack     codeword lookup + bit-length scan + pack  <- Compressor.cu:50-61,541-576,182-313
 #include <mutex>
@@ -24,6 +25,42 @@ hipError_t ensure_lds_limit(const void* fn, int bytes) {
     if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) != hipSuccess) return e;
     done.insert(key);
     return hipSuccess;
+}
+
+// Table upload (hz_internal.h StageSeg): every table set of a codebook, whichever stage reads it.
+struct StageArgs {
+    const uint8_t* src;
+    StageSeg seg[kStageMaxSegs];
+};
+// Segment blockIdx.y of the staging buffer to its table: 16-byte vectors, then the 4-byte tail.
+__global__ __launch_bounds__(256) void k_stage_scatter(StageArgs a) {
+    const StageSeg g = a.seg[blockIdx.y];
+    const uint4* src = reinterpret_cast<const uint4*>(a.src + g.off);
+    uint4* dst = reinterpret_cast<uint4*>(g.dst);
+    const uint64_t nv = g.bytes / 16;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (uint64_t)gridDim.x * blockDim.x)
+        dst[i] = src[i];
+    if (blockIdx.x == 0 && threadIdx.x < (g.bytes % 16) / 4) {
+        const uint64_t w = nv * 4 + threadIdx.x;
+        reinterpret_cast<uint32_t*>(g.dst)[w] = reinterpret_cast<const uint32_t*>(a.src + g.off)[w];
+    }
+}
+
+hipError_t stage_scatter(const uint8_t* h_src, const StageSeg* segs, int nseg, hipStream_t s) {
+    for (int i0 = 0; i0 < nseg; i0 += kStageMaxSegs) {
+        StageArgs a;
+        a.src = h_src;
+        const int n = nseg - i0 < kStageMaxSegs ? nseg - i0 : kStageMaxSegs;
+        uint64_t most = 0;
+        for (int i = 0; i < n; ++i) {
+            a.seg[i] = segs[i0 + i];
+            most = a.seg[i].bytes > most ? a.seg[i].bytes : most;
+        }
+        uint64_t blocks = (most / 16 + 255) / 256;
+        blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
+        hipLaunchKernelGGL(k_stage_scatter, dim3((uint32_t)blocks, (uint32_t)n), dim3(256), 0, s, a);
+    }
+    return hipGetLastError();
 }
 
 // ===========================================================================

@@ -1,6 +1,11 @@
-"""The build's file lists are derived from the source directory, and its job count is bounded."""
+"""The build's file lists are derived from the source directory, its job count is bounded, and every
+header compiles on its own."""
+import concurrent.futures
 import os
 import shutil
+import subprocess
+
+import pytest
 
 from huffman_amd import build
 
@@ -25,6 +30,25 @@ def test_source_id_follows_a_header(tmp_path):
         f.write(b"\n")
     assert build.source_id(str(src), str(inc)) != before
     assert build.source_id() == before  # the tree itself is untouched
+
+
+@pytest.mark.skipif(not os.path.exists(build.HIPCC), reason="no hipcc")
+def test_every_header_compiles_alone(tmp_path):
+    """A unit that holds nothing but the header compiles for the device with the build's flags, so no
+    header depends on what its includer happened to include first."""
+    names = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".h"))
+    assert names
+
+    def check(name):
+        tu = tmp_path / (name + ".hip")
+        tu.write_text(f'#include "{name}"\n')
+        cmd = [build.HIPCC] + build.CFLAGS + [f"-I{build.INCLUDE}", f"-I{build.CSRC}", "-x", "hip",
+                                              "--cuda-device-only", "-fsyntax-only", str(tu)]
+        return name, subprocess.run(cmd, capture_output=True, text=True)
+
+    with concurrent.futures.ThreadPoolExecutor(build.build_jobs(len(names))) as pool:
+        for name, r in pool.map(check, names):
+            assert r.returncode == 0, f"{name}:\n{r.stderr}"
 
 
 def test_job_count_is_bounded(monkeypatch):
