@@ -23,26 +23,6 @@
 #include "huffman_amd.h"
 #include "hz_internal.h"
 
-namespace hz {
-int select_enc_mode(const hz_codebook* cb);
-std::vector<uint32_t> build_enc_dense(const hz_codebook* cb);
-std::vector<uint32_t> build_enc_fixed16(const hz_codebook* cb);
-std::vector<uint32_t> build_dec_fixed16(const hz_codebook* cb);
-std::vector<uint32_t> build_enc_hot(const hz_codebook* cb, uint32_t m);
-uint32_t choose_hot_mask(const hz_codebook* cb);
-std::vector<uint32_t> build_enc_esc(const hz_codebook* cb, uint32_t m);
-std::vector<uint32_t> build_len8(const hz_codebook* cb);
-std::vector<uint32_t> build_lenpair(const hz_codebook* cb);
-std::vector<uint64_t> build_enc_wide(const hz_codebook* cb);
-int select_dec_mode(const hz_codebook* cb);
-int build_dec_dense(const hz_codebook* cb, std::vector<uint32_t>& img, int& K);
-int build_dec_lut(const hz_codebook* cb, std::vector<uint32_t>& img, std::vector<uint32_t>& l2, int& K1, int& lvl);
-void build_walk_len(const hz_codebook* cb, std::vector<uint32_t>& img, std::vector<uint32_t>& esc, int& K, int& M,
-                    int& bias);
-void build_walk8(const hz_codebook* cb, std::vector<uint32_t>& img, int& K);
-void build_chain_esc(const hz_codebook* cb, std::vector<uint32_t>& img, int& M);
-}  // namespace hz
-
 using namespace hz;
 
 // HZ_DEBUG=1: a failing HIP call is named on stderr (file line, call, HIP's message) before HZ_EHIP.

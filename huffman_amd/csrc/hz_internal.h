@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "huffman_amd.h"
 
 namespace hz {
@@ -245,6 +247,26 @@ __host__ __device__ inline uint32_t hot_slot(uint32_t s, uint32_t m) { return (s
 // LDS word of a HOT slot: the symbol's second byte is XORed into the bank bits
 // (the first byte alone would pick the bank; skewed data keeps it small).
 __host__ __device__ inline uint32_t hot_word(uint32_t slot) { return slot ^ ((slot >> 8) & 0x3fu); }
+
+// Host builders of the table images (hz_codebook.cpp): the mode a codebook takes, and every image the
+// uploads (hz_host.cpp) and the table probe (tests/table_probe.cpp) build from it.
+int select_enc_mode(const hz_codebook* cb);
+std::vector<uint32_t> build_enc_dense(const hz_codebook* cb);
+std::vector<uint32_t> build_enc_fixed16(const hz_codebook* cb);
+std::vector<uint32_t> build_dec_fixed16(const hz_codebook* cb);
+std::vector<uint32_t> build_enc_hot(const hz_codebook* cb, uint32_t m);
+uint32_t choose_hot_mask(const hz_codebook* cb);
+std::vector<uint32_t> build_enc_esc(const hz_codebook* cb, uint32_t m);
+std::vector<uint32_t> build_len8(const hz_codebook* cb);
+std::vector<uint32_t> build_lenpair(const hz_codebook* cb);
+std::vector<uint64_t> build_enc_wide(const hz_codebook* cb);
+int select_dec_mode(const hz_codebook* cb);
+int build_dec_dense(const hz_codebook* cb, std::vector<uint32_t>& img, int& K);
+int build_dec_lut(const hz_codebook* cb, std::vector<uint32_t>& img, std::vector<uint32_t>& l2, int& K1, int& lvl);
+void build_walk_len(const hz_codebook* cb, std::vector<uint32_t>& img, std::vector<uint32_t>& esc, int& K, int& M,
+                    int& bias);
+void build_walk8(const hz_codebook* cb, std::vector<uint32_t>& img, int& K);
+void build_chain_esc(const hz_codebook* cb, std::vector<uint32_t>& img, int& M);
 
 // Launchers, by the file that defines them. All stream ordered; return hipError_t.
 // ---- hz_hist.hip ------------------------------------------------------------

@@ -12,8 +12,8 @@ Every device result is compared with the model (never only with another device r
 output and index buffer sits between 64-byte guards of 0xA5. A device-side status at hz_ctx_sync
 counts as a failure of the check that raised it.
 
-Run as a script (`python tests/test_gpu_designed_streams.py pipe`) it runs the fib57, hot25 and
-dense16 cases once and prints "ok": the tests start it in a fresh process per HZ_DEC_PIPE value,
+Run as a script (`python tests/test_gpu_designed_streams.py pipe`) it runs the fib57, hot25,
+dense16 and zipf21 cases once and prints "ok": the tests start it in a fresh process per HZ_DEC_PIPE value,
 which the library reads once.
 
 Tolerance: none -- every check is bit-exact."""
@@ -21,7 +21,6 @@ import os
 import subprocess
 import sys
 import zlib
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -31,6 +30,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ref_stream  # noqa: E402
+import table_model  # noqa: E402
+from table_books import book  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -41,75 +42,18 @@ HZ_EHIP = -3
 UNKNOWN_ENTRY = (1 << 64) - 1
 LEAD_BITS = 1024  # HZ_INDEXLESS_LEAD_BITS
 
-BOOKS = ["fib57", "fib41", "hot25", "dense16", "dense12", "even", "fixed16"]
+BOOKS = ["fib57", "fib41", "hot25", "dense16", "dense12", "even", "fixed16", "zipf21", "sq32"]
+FULL_BOOKS = ["zipf21", "sq32"]   # whole 65 536-symbol alphabets: the benchmark's table classes (tests/table_books.py)
 KINDS = ["longest", "shortest", "blocks", "chains", "uniform"]
+FULL_KINDS = ["sweep", "escapes"]  # the kinds of the full books only
 EDGE_SIZES = [1, 7, 8, 9, 2047, 2048, 2049, 3 * BLK + 5]
 START_BITS = [0, 5, 31, 32, 45]
 WAVES = 40 * BLK + 777       # about 40 blocks and a ragged tail: several waves
 ALL_CUS = 600 * BLK + 1234   # about 600 blocks: every CU (below 2^21 symbols)
+SWEEP = 2 * 65536 + 5        # a full book's sweep: the alphabet twice and a ragged tail, about 64 blocks
 
 
-# ---- codebooks --------------------------------------------------------------------------------
-def _fib_hist(k):
-    fib = [1, 1]
-    while len(fib) < k:
-        fib.append(fib[-1] + fib[-2])
-    syms = (np.arange(k, dtype=np.uint32) * 257 + 3).astype(np.uint16)
-    hist = np.zeros(65536, dtype=np.uint64)
-    hist[syms] = fib
-    return hist, syms
-
-
-def _book(name):
-    """A codebook by name, with the shape it claims asserted: (Codebook, len[], code[])."""
-    from huffman_amd import build_codebook, codebook_arrays
-    hist = np.zeros(65536, dtype=np.uint64)
-    if name in ("fib57", "fib41"):
-        hist, syms = _fib_hist(int(name[3:]))
-    elif name == "hot25":     # weights 2^i: a path of 26 leaves, the walker's escape table at its limit
-        hist[np.arange(25) * 257] = [1 << i for i in range(25)]
-        hist[25 * 257] = 1
-    elif name == "dense16":   # 40 000 equal counts: 15 and 16 bits (DENSE, no room for output slots)
-        hist[:40000] = 1
-    elif name == "dense12":   # 3000 equal counts: 11 and 12 bits (DEC_DENSE)
-        hist[np.arange(3000) * 19 + 7] = 1
-    elif name == "even":      # every length even: an odd-bit entry never resynchronises
-        hist[np.arange(10) * 1000 + 1] = [16, 16, 16, 4, 4, 4, 1, 1, 1, 1]
-    elif name == "fixed16":
-        hist[:] = 1
-    else:
-        raise ValueError(name)
-    cb = build_codebook(hist)
-    _, ln, code = codebook_arrays(cb)
-    used = ln[ln > 0]
-    lo, hi = int(used.min()), int(used.max())
-    assert (cb.min_len, cb.max_len) == (lo, hi)
-    if name == "fib57":
-        assert (lo, hi) == (1, 56) and sorted(ln[syms[:8]].tolist()) == [50, 51, 52, 53, 54, 55, 56, 56]
-    elif name == "fib41":
-        assert (lo, hi) == (1, 40) and int(ln[syms[:8]].min()) >= 33
-    elif name == "hot25":
-        assert (lo, hi) == (1, 25) and used.size == 26
-    elif name == "dense16":
-        assert (lo, hi) == (15, 16) and used.size == 40000
-    elif name == "dense12":
-        assert (lo, hi) == (11, 12) and used.size == 3000
-    elif name == "even":
-        assert ln[np.arange(10) * 1000 + 1].tolist() == [2, 2, 2, 4, 4, 4, 6, 6, 6, 6]
-    elif name == "fixed16":
-        assert (lo, hi) == (16, 16) and used.size == 65536
-    return SimpleNamespace(name=name, cb=cb, ln=ln, code=code)
-
-
-_books = {}
-
-
-def book(name):
-    if name not in _books:
-        _books[name] = _book(name)
-    return _books[name]
-
-
+# ---- codebooks: tests/table_books.py (book(name) -> name, cb, ln, code) --------------------------
 # ---- streams ----------------------------------------------------------------------------------
 def _stream(bk, kind, nsym, rng):
     """u16 symbols drawn by design, not from the codebook's histogram."""
@@ -132,9 +76,35 @@ def _stream(bk, kind, nsym, rng):
         sym = np.where((i + i // 8) % 2 == 0, draw(longest, nsym), draw(shortest, nsym))
     elif kind == "uniform":
         sym = draw(alphabet, nsym)
+    elif kind == "sweep":
+        # the whole alphabet once in a seeded permutation (every symbol, followed by arbitrary codes), then
+        # again sorted by code length, descending (whole blocks of only-longest codes from thousands of
+        # distinct symbols, every symbol followed by a long code), and a ragged tail
+        by_len = alphabet[np.argsort(-lens, kind="stable")]
+        sym = np.concatenate([rng.permutation(alphabet), by_len, by_len[:5]])
+        assert sym.size == nsym == 2 * alphabet.size + 5
+    elif kind == "escapes":
+        pool = escape_pool(bk)
+        sym = draw(pool if pool.size else longest, nsym)
     else:
         raise ValueError(kind)
     return np.ascontiguousarray(sym, dtype="<u2")
+
+
+def escape_pool(bk):
+    """The symbols that sit on the tables' rare paths: they resolve past level 1 of the decode LUT (codes
+    longer than its 13 bits) and, under a HOT book, also miss their slot (tests/table_model.py's ownership
+    rule under its own choice of the pairing mask). Empty for the older books: `escapes` is `longest` there."""
+    if bk.name not in FULL_BOOKS:
+        return np.zeros(0, np.uint16)
+    ln = bk.ln
+    past = ln > table_model.K_DEC_LUT_MAX_K1
+    if int(ln.max()) <= table_model.K_HOT_MAX_LEN:    # ENC_HOT
+        miss = [table_model.hot_miss_mass(ln, m) for m in table_model.HOT_MASKS]
+        past &= ~table_model.hot_owner(ln, table_model.HOT_MASKS[int(np.argmin(miss))])
+    pool = np.nonzero(past)[0].astype(np.uint16)
+    assert pool.size >= 1000, (bk.name, pool.size)
+    return pool
 
 
 def _lead(start_bit):
@@ -156,6 +126,17 @@ def _cases():
             if case not in out:
                 out.append(case)
         out.append((b, "blocks", ALL_CUS, START_BITS[(3 + bi) % 5]))
+    # the full books meet the two kinds of their own as well
+    for bi, b in enumerate(FULL_BOOKS):
+        out.append((b, "sweep", SWEEP, START_BITS[(bi + 1) % 5]))
+        out.append((b, "escapes", WAVES, START_BITS[(bi + 3) % 5]))
+    # every size edge and every start bit with zipf21 (no case of a full book is larger than its sweep)
+    sized = KINDS + ["escapes"]
+    for si, nsym in enumerate(EDGE_SIZES):
+        case = ("zipf21", sized[(si + 3) % 6], nsym, START_BITS[(si + 1) % 5])
+        if case not in out:
+            out.append(case)
+    out.append(("zipf21", "sweep", SWEEP, 45))
     return out
 
 
@@ -169,10 +150,15 @@ def _case_id(case):
 def test_case_matrix_is_complete():
     """The cross product is not run in full; this is what must appear."""
     for b in BOOKS:
-        assert {k for bb, k, _, _ in CASES if bb == b} == set(KINDS), b
+        assert {k for bb, k, _, _ in CASES if bb == b} == set(KINDS + FULL_KINDS if b in FULL_BOOKS else KINDS), b
     for b in ("fib57", "hot25", "dense16"):
         assert {n for bb, _, n, _ in CASES if bb == b} >= set(EDGE_SIZES) | {WAVES, ALL_CUS}, b
         assert {s for bb, _, _, s in CASES if bb == b} == set(START_BITS), b
+    assert {n for bb, _, n, _ in CASES if bb == "zipf21"} >= set(EDGE_SIZES) | {WAVES, SWEEP}
+    assert {s for bb, _, _, s in CASES if bb == "zipf21"} == set(START_BITS)
+    assert ("zipf21", "sweep", SWEEP, 45) in CASES and len([c for c in CASES if c[:2] == ("zipf21", "sweep")]) == 2
+    assert max(n for bb, _, n, _ in CASES if bb in FULL_BOOKS) <= SWEEP
+    assert len(set(CASES)) == len(CASES)
     assert max(n for _, _, n, _ in CASES) <= 1 << 21
 
 
@@ -448,7 +434,7 @@ def _child(env):
 @pytest.mark.parametrize("pipe", ["0", "1"])
 def test_decoder_forms(built_lib, pipe):
     """HZ_DEC_PIPE=0 / 1 (2 is the default, every other test): the plain and the one-block pipelined forms
-    of the block decoder on the fib57, hot25 and dense16 cases."""
+    of the block decoder on the fib57, hot25, dense16 and zipf21 cases."""
     _child({"HZ_DEC_PIPE": pipe})
 
 
@@ -458,7 +444,7 @@ if __name__ == "__main__":
     _c = StreamCodec(0)
     _bad = []
     for _case in CASES:
-        if _case[0] in ("fib57", "hot25", "dense16") and _case[2] != ALL_CUS:
+        if _case[0] in ("fib57", "hot25", "dense16", "zipf21") and _case[2] != ALL_CUS:
             _bad += [_case_id(_case) + " " + f for f in run_case(_c, _case)]
     if _bad:
         print("\n".join(_bad))
