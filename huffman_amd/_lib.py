@@ -16,6 +16,7 @@ HZ_MAXLEN = 56
 HZ_RANGE_LEAD_BYTES = 32
 HZ_RANGE_TAIL_BYTES = 32
 HZ_RANGE_FULL_INDEX = 1
+HZ_RANGES_STATS_WORDS = 4
 
 STATUS = {
     0: "HZ_OK", -1: "HZ_EINVAL", -2: "HZ_ENOMEM", -3: "HZ_EHIP", -4: "HZ_ETOOLONG",
@@ -104,6 +105,7 @@ PROTOTYPES = [
     ("hz_seek_bytes", _U64, [_U64]),
     ("hz_seek_span", _I, [_P, _U64, _U64, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hz_decode_range", _I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _P, _U32]),
+    ("hz_decode_ranges", _I, [_P, _P, _U64, _U64, _P, _U64, _P, _U32, _P, _U64, _P, _U32]),
     ("hz_index_expand", _I, [_P, _P, _U64, _P, _U64, _P]),
     ("hz_decode_indexless", _I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     ("hz_indexless_scan", _I, [_P, _P, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _P]),
@@ -121,6 +123,7 @@ PROTOTYPES = [
     ("hz_decode_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_seek_build_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_decode_range_host", _I, [_P, _U64, _P, _U64, _U64, _P]),
+    ("hz_decode_ranges_host", _I, [_P, _U64, _P, _P, _P, _U32, _P]),
 ]
 
 _lib = None

@@ -185,6 +185,22 @@ def decode_range(blob, seek, offset, length):
     return out[:length].tobytes()
 
 
+def decode_ranges(blob, seek, ranges):
+    """[(offset, length), ...] byte ranges of the original from a .compressed image and its seek table,
+    decoded in one device call (hz_decode_ranges_host): a list of bytes, in the ranges' order."""
+    lib = load()
+    arr, p = _buf(blob)
+    sk = np.ascontiguousarray(seek, dtype=np.uint64)
+    offs = np.array([int(o) for o, _ in ranges], dtype=np.uint64)
+    cnts = np.array([int(c) for _, c in ranges], dtype=np.uint64)
+    out = np.empty(max(int(cnts.sum()), 1), dtype=np.uint8)
+    check(lib.hz_decode_ranges_host(p, arr.size, sk.ctypes.data_as(ctypes.c_void_p), offs.ctypes.data_as(ctypes.c_void_p),
+                                    cnts.ctypes.data_as(ctypes.c_void_p), offs.size,
+                                    out.ctypes.data_as(ctypes.c_void_p)), "hz_decode_ranges_host")
+    ends = np.cumsum(cnts).astype(np.int64)
+    return [out[int(e) - int(c):int(e)].tobytes() for e, c in zip(ends, cnts)]
+
+
 class Device:
     """Stage API on device pointers (ints), stream-ordered on one HIP stream."""
 
@@ -278,6 +294,14 @@ class Device:
         check(self.lib.hz_decode_range(self.h, d_payload, payload_bytes, payload_byte_base, d_seek, nsym, sym_begin,
                                        sym_count, d_out, _lib.HZ_RANGE_FULL_INDEX if full_index else 0),
               "hz_decode_range")
+
+    def decode_ranges(self, d_payload, payload_bytes, d_seek, nsym, d_ranges, nranges, d_out, out_bytes, d_stats=None,
+                      full_index=False, payload_byte_base=0):
+        """A batch of ranges in one call (hz_decode_ranges). d_ranges: nranges x (sym_begin, sym_count,
+        out_byte) u64 on the device, range i into d_out + out_byte; d_stats: 4 u64 on the device, or None."""
+        check(self.lib.hz_decode_ranges(self.h, d_payload, payload_bytes, payload_byte_base, d_seek, nsym, d_ranges,
+                                        nranges, d_out, out_bytes, d_stats,
+                                        _lib.HZ_RANGE_FULL_INDEX if full_index else 0), "hz_decode_ranges")
 
     def index_expand(self, d_payload, payload_bytes, d_seek, nsym, d_index):
         """Seek table -> the complete block index (d_seek may be d_index)."""

@@ -10,7 +10,7 @@
 
 #include <type_traits>
 
-#include "hz_decode_device.h"
+#include "hz_range_device.h"
 
 namespace hz {
 
@@ -476,17 +476,6 @@ __global__ __launch_bounds__(PIPE == 2 ? kDecPipe2Threads : 1024) void k_decode(
     }
 }
 
-// The FIXED16 step: five byte-swapped stream words whose bit pos % 32 is a code's first bit -> the
-// eight symbols of the next 128 bits as four output words.
-HZ_DEV void fixed16_step(const uint16_t* t16, const uint32_t (&ww)[5], uint32_t pos, uint32_t (&o)[4]) {
-    const uint32_t sh = pos & 31;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const uint32_t cw = sh ? __builtin_amdgcn_alignbit(ww[t], ww[t + 1], 32u - sh) : ww[t];
-        o[t] = (uint32_t)t16[cw >> 16] | ((uint32_t)t16[cw & 0xffffu] << 16);
-    }
-}
-
 // Every code 16 bits: lane j decodes symbols [32 j, 32 j + 32) from the 17
 // words starting at stream word (p0 >> 5) + 16 j.
 // Full blocks [0, nb) of a FIXED16 stream (k_pack_fixed16_blk's mapping): lane l's sub-run c decodes the block's symbols 8 (64 c + l) .. + 7 from 4 words at a
@@ -585,14 +574,7 @@ __global__ __launch_bounds__(1024) void k_decode_fixed16(DecArgs a, uint64_t nb)
     }
 }
 
-// The random access view of the block decoders (DESIGN.md "Random access"; launchers below).
-struct RangeDecArgs : DecArgs {
-    uint64_t w_first;    // first word of the view that exists (words below it are only addressed, never read)
-    const uint8_t* bad;  // per tile block: nonzero = failed a check, nothing is stored for it
-    uint64_t blk0;       // the tile's first block in the stream (a.starts / a.subs / a.nblocks are the tile's)
-    uint64_t lo, hi;     // stream symbols [lo, hi) go to out + 2 (sym - lo); nothing else is written
-};
-
+// The random access view of the block decoders (RangeDecArgs): hz_range_device.h; launchers below.
 // dec_stage_prefetch for a moved view: chunks outside the payload read the view's first real chunk
 // (dec_stage_commit zero-fills them as it does for the plain view's word 0).
 template <int NS>
@@ -802,17 +784,7 @@ hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t pay
 // stream bits, the view's word 0 is moved down instead (never dereferenced below
 // w_first).
 // ===========================================================================
-struct SeekArgs {
-    const unsigned long long* seek;  // the stream's start[]: block b at seek[b]
-    const unsigned long long* isub;  // a full index's sub rows (chain 0 is checked against start[b]); else null
-    unsigned long long* tstart;      // the tile's index in scratch: start[nb + 1] clamped into the view; null: none
-    unsigned long long* rows;        // sub rows out, 64 words per block of the tile
-    unsigned long long* maxp;        // the tile's largest block in bits (atomicMax; zeroed by the launcher)
-    uint8_t* bad;                    // per block of the tile; null: none
-    uint64_t blk0, nb, nsym;
-    uint64_t clamp_lo, bit_hi;       // stream bits a block may start at / end at inside the view
-};
-
+// (SeekArgs, the per-block checks and fill_range_view: hz_range_device.h, shared with hz_ranges.hip.)
 constexpr int kSeekThreads = 256;
 
 // One lane per block of the tile. Checks: start[b] <= start[b + 1] and at most cnt * max_len bits apart
@@ -832,7 +804,7 @@ __global__ __launch_bounds__(kSeekThreads) void k_seek_subs(DecArgs a, SeekArgs 
         const uint64_t s0 = y.seek[b], s1 = y.seek[b + 1];
         const uint64_t left = y.nsym - b * kBlockSyms;
         const uint32_t cnt = left < (uint64_t)kBlockSyms ? (uint32_t)left : (uint32_t)kBlockSyms;
-        uint32_t err = 0;
+        uint32_t err = 0;  // (seek_block_err's checks in place: through the function the kernel compiles to other instructions)
         if (s1 < s0 || s1 - s0 > (uint64_t)cnt * (uint32_t)a.max_len) err = 1u;
         else if (s0 < y.clamp_lo || s1 > y.bit_hi) err = 16u;
         else if (y.isub && (uint32_t)(y.isub[b * kWave] & 0xffffu) != (uint32_t)(s0 & 0xffffu)) err = 1u;
@@ -938,29 +910,6 @@ uint64_t range_scratch_words(uint64_t sym_begin, uint64_t sym_count) {
     const uint64_t Tf = nb < kRangeFullTileFactor * range_tile_blocks() ? nb : kRangeFullTileFactor * range_tile_blocks();
     const uint64_t seek = (T + 2) + (T + 7) / 8 + (uint64_t)kWave * T, full = (Tf + 2) + (Tf + 7) / 8;
     return seek > full ? seek : full;  // either mode, so a context's scratch settles after one call
-}
-
-// The view of a payload slice that holds stream bytes [base, base + payload_bytes): stream bit p is
-// bit p + bit_adj of `words`, whose word 0 lies below the slice when base > 0.
-static void fill_range_view(RangeDecArgs& a, SeekArgs& y, const Tables& t, const uint8_t* d_payload,
-                            uint64_t payload_bytes, uint64_t base, uint64_t nsym) {
-    fill_dec_args(a, t, d_payload, payload_bytes, nsym);
-    const uint64_t head = (uintptr_t)d_payload & 63, r = base & 63;
-    uint64_t shift = base >> 6;  // 64-byte units the view's word 0 moves down
-    uint64_t adj = head - r;
-    if (head < r) { adj = head + 64 - r; shift += 1; }
-    a.words = reinterpret_cast<const uint32_t*>(((uintptr_t)d_payload & ~(uintptr_t)63) - 64 * shift);
-    a.bit_adj = (uint32_t)(8 * adj);
-    a.w_first = 16 * shift;
-    a.nwords = a.w_first + (payload_bytes + head + 3) / 4;
-    a.start0 = 0;
-    // a block's staging window starts 16 bytes below the 16-byte chunk of its first bit: inside the slice
-    // unless the slice starts the stream (base 0: words below the payload read as zeros, as in hz_decode)
-    const uint64_t vlo = 8 * base + a.bit_adj;
-    y.clamp_lo = base ? 128 * ((vlo + 127) / 128 + 1) - a.bit_adj : 0;
-    y.bit_hi = 8 * (base + payload_bytes);
-    if (y.clamp_lo > y.bit_hi) y.clamp_lo = y.bit_hi;  // a slice too small for any block: every block fails
-    y.nsym = nsym;
 }
 
 template <int MODE, bool WALK>

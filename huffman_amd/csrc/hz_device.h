@@ -83,6 +83,16 @@ HZ_DEV uint32_t pick4(const uint4& v, uint32_t i) {
     return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w));
 }
 
+// Position (0..31) of the r-th (0-based) set bit of m; r < popc(m).
+HZ_DEV uint32_t select_bit(uint32_t m, uint32_t r) {
+    uint32_t pos = 0, c;
+    c = __popc(m & 0xffffu); if (r >= c) { r -= c; pos += 16; m >>= 16; }
+    c = __popc(m & 0xffu);   if (r >= c) { r -= c; pos += 8;  m >>= 8; }
+    c = __popc(m & 0xfu);    if (r >= c) { r -= c; pos += 4;  m >>= 4; }
+    c = __popc(m & 0x3u);    if (r >= c) { r -= c; pos += 2;  m >>= 2; }
+    return pos + ((r >= (m & 1u)) ? 1u : 0u);
+}
+
 HZ_DEV void copy_lds_table(uint32_t* lds, const uint32_t* img, uint32_t words) {
     const uint4* src = reinterpret_cast<const uint4*>(img);
     uint4* dst = reinterpret_cast<uint4*>(lds);

@@ -621,6 +621,26 @@ extern "C" int hz_decode_range(hz_ctx* c, const uint8_t* d_payload, uint64_t pay
     return arm_err_check(c);
 }
 
+extern "C" int hz_decode_ranges(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t payload_byte_base,
+                                const uint64_t* d_seek, uint64_t nsym, const hz_range* d_ranges, uint32_t nranges,
+                                uint8_t* d_out, uint64_t out_bytes, uint64_t* d_stats, uint32_t flags) {
+    if (!c || !d_payload || !d_seek || !d_ranges || !d_out) return HZ_EINVAL;
+    if ((flags & ~HZ_RANGE_FULL_INDEX) || (((uintptr_t)d_out) & 1)) return HZ_EINVAL;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    if (nranges == 0) return HZ_OK;
+    HZ_TRY(hipSetDevice(c->device));
+    int rc = ensure_scratch(c, ranges_scratch_words(nranges));
+    if (rc) return rc;
+    HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 0));
+    HZ_TRY(launch_decode_ranges(c->t, d_payload, payload_bytes, payload_byte_base,
+                                reinterpret_cast<const unsigned long long*>(d_seek), nsym, d_ranges, nranges, d_out,
+                                out_bytes, reinterpret_cast<unsigned long long*>(d_stats),
+                                (flags & HZ_RANGE_FULL_INDEX) != 0, c->d_desc, c->d_err, c->ncu, c->stream));
+    HZ_TRY(stage_event(c, HZ_STAGE_DECODE, 1));
+    c->ev_used[HZ_STAGE_DECODE] = true;
+    return arm_err_check(c);
+}
+
 extern "C" int hz_index_expand(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, const uint64_t* d_seek,
                                uint64_t nsym, uint64_t* d_index) {
     if (!c) return HZ_EINVAL;
@@ -1018,6 +1038,74 @@ int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uin
         memcpy(out, tmp.data() + skip, std::min<uint64_t>(count, tmp.size() - skip));
     }
     if (info.is_odd && offset + count == info.n) out[count - 1] = (uint8_t)info.last_byte;
+    return HZ_OK;
+}
+
+// Byte ranges [offsets[i], offsets[i] + counts[i]) of the original, concatenated in `out`: one
+// hz_decode_ranges call over one payload slice (the smallest byte_begin to the largest byte_end).
+int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
+                        const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    std::unique_ptr<hz_codebook> cb(new hz_codebook());
+    hz_header_info info;
+    int rc = hz_header_parse(f, len, cb.get(), &info);
+    if (rc) return rc;
+    if (nranges == 0) return HZ_OK;
+    if (!offsets || !counts) return HZ_EINVAL;
+    const uint64_t nsym = info.n / 2, pay = len - info.payload_byte;
+    std::vector<hz_range> rg(nranges);
+    uint64_t tmp_bytes = 0, total = 0, bb = UINT64_MAX, be = 0, b0 = UINT64_MAX, b1 = 0;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (offsets[i] > info.n || counts[i] > info.n - offsets[i]) return HZ_EINVAL;
+        const uint64_t s0 = offsets[i] / 2, s1 = std::min((offsets[i] + counts[i] + 1) / 2, nsym);  // covering symbols
+        rg[i].sym_begin = s0;
+        rg[i].sym_count = counts[i] && s1 > s0 ? s1 - s0 : 0;
+        rg[i].out_byte = tmp_bytes;
+        tmp_bytes += 2 * rg[i].sym_count;
+        total += counts[i];
+        if (rg[i].sym_count) {
+            if (!seek) return HZ_EINVAL;
+            uint64_t rb, re;
+            if ((rc = hz_seek_span(seek, nsym, s0, rg[i].sym_count, &rb, &re))) return rc;
+            bb = std::min(bb, rb);
+            be = std::max(be, re);
+            b0 = std::min(b0, s0 / kBlockSyms);
+            b1 = std::max(b1, (s1 - 1) / kBlockSyms);
+        }
+    }
+    if (total && !out) return HZ_EINVAL;
+    std::vector<uint8_t> tmp(tmp_bytes);
+    if (tmp_bytes) {
+        if (bb >= pay) return HZ_EFORMAT;
+        be = std::min(be, pay);
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload_decode(c, cb.get()))) return rc;
+        DevBuf dpay, dseek, drg, dout;
+        if ((rc = dpay.alloc(be - bb + 16))) return rc;
+        HZ_TRY(hipMemsetAsync(dpay.p, 0, be - bb + 16, c->stream));
+        HZ_TRY(hipMemcpyAsync(dpay.p, f + info.payload_byte + bb, be - bb, hipMemcpyHostToDevice, c->stream));
+        if ((rc = dseek.alloc(8 * (b1 - b0 + 2)))) return rc;
+        HZ_TRY(hipMemcpyAsync(dseek.p, seek + b0, 8 * (b1 - b0 + 2), hipMemcpyHostToDevice, c->stream));
+        if ((rc = drg.alloc(sizeof(hz_range) * (uint64_t)nranges))) return rc;
+        HZ_TRY(hipMemcpyAsync(drg.p, rg.data(), sizeof(hz_range) * (uint64_t)nranges, hipMemcpyHostToDevice, c->stream));
+        if ((rc = dout.alloc(tmp_bytes))) return rc;
+        // the device reads entries b0 .. b1 + 1 only, addressed from entry 0
+        const uint64_t* d_seek0 = (const uint64_t*)dseek.p - b0;
+        if ((rc = hz_decode_ranges(c, (const uint8_t*)dpay.p, be - bb, bb, d_seek0, nsym, (const hz_range*)drg.p, nranges,
+                                   (uint8_t*)dout.p, tmp_bytes, nullptr, 0)))
+            return rc;
+        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+    }
+    uint8_t* o = out;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (!counts[i]) continue;
+        const uint64_t skip = offsets[i] - 2 * rg[i].sym_begin, have = 2 * rg[i].sym_count;
+        if (have > skip) memcpy(o, tmp.data() + rg[i].out_byte + skip, std::min<uint64_t>(counts[i], have - skip));
+        if (info.is_odd && offsets[i] + counts[i] == info.n) o[counts[i] - 1] = (uint8_t)info.last_byte;
+        o += counts[i];
+    }
     return HZ_OK;
 }
 
@@ -1829,6 +1917,12 @@ extern "C" int hz_decode_range_host(const uint8_t* file, uint64_t len, const uin
                                     uint64_t count, uint8_t* out) {
     if (!file) return HZ_EINVAL;
     return guarded([&] { return decode_range_image(file, len, seek, offset, count, out); });
+}
+
+extern "C" int hz_decode_ranges_host(const uint8_t* file, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
+                                     const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&] { return decode_ranges_image(file, len, seek, offsets, counts, nranges, out); });
 }
 
 // Compressor.cu:315-632, stdout lines kept (:335-336,385,612-631).

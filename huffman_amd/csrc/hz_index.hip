@@ -497,16 +497,6 @@ __global__ __launch_bounds__(kSyncThreads) void k_sync_iter(DecArgs a, SyncArgs 
     }
 }
 
-// Position (0..31) of the r-th (0-based) set bit of m; r < popc(m).
-HZ_DEV uint32_t select_bit(uint32_t m, uint32_t r) {
-    uint32_t pos = 0, c;
-    c = __popc(m & 0xffffu); if (r >= c) { r -= c; pos += 16; m >>= 16; }
-    c = __popc(m & 0xffu);   if (r >= c) { r -= c; pos += 8;  m >>= 8; }
-    c = __popc(m & 0xfu);    if (r >= c) { r -= c; pos += 4;  m >>= 4; }
-    c = __popc(m & 0x3u);    if (r >= c) { r -= c; pos += 2;  m >>= 2; }
-    return pos + ((r >= (m & 1u)) ? 1u : 0u);
-}
-
 // One workgroup per tile of kSelTileSegs bitmap rows (64 Kbit); thread t
 // holds words [8 t, 8 t + 8). A workgroup scan of popcounts numbers every
 // boundary from the tile's first (first[] of its first row). Boundary i < nsym

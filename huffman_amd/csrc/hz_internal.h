@@ -1,5 +1,5 @@
 // hz_internal.h -- shared layout constants and launch interfaces between the
-// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_decode.hip,
+// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_decode.hip, hz_ranges.hip,
 // hz_index.hip, hz_chain.hip, hz_codebook_gpu.hip; DESIGN.md "Source layout").
 #pragma once
 #include <hip/hip_runtime.h>
@@ -309,6 +309,15 @@ hipError_t launch_decode_range(const Tables& t, const uint8_t* d_payload, uint64
 hipError_t launch_index_expand(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                                const unsigned long long* d_seek, uint64_t nsym, unsigned long long* d_index,
                                uint32_t* d_err, hipStream_t s);
+// ---- hz_ranges.hip ----------------------------------------------------------
+// A batch of ranges (DESIGN.md "A batch of ranges"): d_ranges and d_stats (nullable) are device memory,
+// the view and the seek table are launch_decode_range's; d_scratch: ranges_scratch_words().
+uint64_t ranges_scratch_words(uint32_t nranges);
+hipError_t launch_decode_ranges(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t base,
+                                const unsigned long long* d_seek, uint64_t nsym, const hz_range* d_ranges,
+                                uint32_t nranges, uint8_t* d_out, uint64_t out_bytes, unsigned long long* d_stats,
+                                bool full_index, unsigned long long* d_scratch, uint32_t* d_err, int ncu,
+                                hipStream_t s);
 // ---- hz_index.hip -----------------------------------------------------------
 hipError_t launch_index_build(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                               uint64_t start_bit, uint64_t nsym, unsigned long long* d_index,

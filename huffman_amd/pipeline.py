@@ -163,6 +163,18 @@ class StreamCodec:
                               out.data_ptr(), full_index, payload_byte_base)
         return out
 
+    def decode_ranges(self, payload, nsym, index, ranges, out, stats=None, full_index=True, payload_byte_base=0):
+        """A batch of ranges of one stream in one call. ranges: an int64 / uint64 device tensor of shape
+        (k, 3), rows (sym_begin, sym_count, out_byte): range i goes to out[out_byte : out_byte + 2 * sym_count].
+        stats: a device tensor of 4 int64 (hz_decode_ranges' d_stats), or None. The call reads `ranges`
+        on the device only, so a captured graph replays with whatever the tensor holds then."""
+        if ranges.dim() != 2 or ranges.shape[1] != 3 or ranges.element_size() != 8 or not ranges.is_contiguous():
+            raise ValueError("ranges: a contiguous (k, 3) tensor of 64-bit integers")
+        self.dev.decode_ranges(payload.data_ptr(), payload.numel(), index.data_ptr(), nsym, ranges.data_ptr(),
+                               ranges.shape[0], out.data_ptr(), out.numel(), None if stats is None else stats.data_ptr(),
+                               full_index, payload_byte_base)
+        return out
+
     def index_expand(self, payload, nsym, seek, index):
         """The complete block index from the seek table (seek may be index itself)."""
         self.dev.index_expand(payload.data_ptr(), payload.numel(), seek.data_ptr(), nsym, index.data_ptr())

@@ -281,6 +281,45 @@ int hz_decode_range(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_byte
                     const uint64_t *d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
                     uint8_t *d_out, uint32_t flags);
 
+/* Many ranges of one stream in one stream-ordered call. d_ranges is a DEVICE array
+ * of nranges entries that the host never reads, so a captured HIP graph can be
+ * replayed with new ranges written into the same array. Range i is symbols
+ * [sym_begin, sym_begin + sym_count) and goes to d_out + out_byte (2 * sym_count
+ * bytes); nothing else of d_out is written. Ranges may overlap, repeat and come in
+ * any order; where their OUTPUT bytes overlap, what lands there is unspecified.
+ * d_payload, payload_bytes, payload_byte_base, d_seek, nsym, the margins and
+ * HZ_RANGE_FULL_INDEX mean what they mean for hz_decode_range; the one slice
+ * covers the hz_seek_span of every range. One wave decodes one block of one
+ * range: from the seek table it finds the block's chain starts cooperatively
+ * (DESIGN.md "A batch of ranges"), with a full index it reads them.
+ * d_stats (nullable, HZ_RANGES_STATS_WORDS u64 on the device, zeroed by the call
+ * in stream order): [0] blocks decoded and stored, [1] blocks that took the cold
+ * path (their payload did not fit a wave's LDS slot), [2] the most fix-up rounds
+ * any block's walk needed (<= 64), [3] blocks flagged (nothing stored for them).
+ * Needs the decode tables and nranges + 2 u64 of the context's scratch: ends a
+ * pending index-less part like every scratch user, and the host waits only when
+ * the scratch must grow. No other host synchronisation and no host copy.
+ * HZ_EINVAL at the call: null pointers (d_stats may be null), unknown flags, an
+ * odd d_out, no decode tables. nranges 0: HZ_OK, nothing launched (d_stats is
+ * left as it was).
+ * Found on the device and reported by hz_ctx_sync: HZ_EINVAL for a range with
+ * sym_begin + sym_count > nsym, an odd out_byte or out_byte + 2 * sym_count >
+ * out_bytes (nothing is written for that range) and for a block whose bytes and
+ * margins are not inside the slice; HZ_EFORMAT for the blocks hz_decode_range
+ * reports it for, and for an invalid code. A flagged block stores nothing; every
+ * other block of every range is decoded. Every walk is bounded by its lane's
+ * segment of the block, by 64 rounds and by the block's end bit, and no load
+ * leaves the bounds hz_decode_range documents. */
+typedef struct hz_range {
+    uint64_t sym_begin;  /* first symbol of the range */
+    uint64_t sym_count;  /* symbols; 0 = nothing written */
+    uint64_t out_byte;   /* even byte offset in d_out of the range's 2 * sym_count bytes */
+} hz_range;
+#define HZ_RANGES_STATS_WORDS 4
+int hz_decode_ranges(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t payload_byte_base,
+                     const uint64_t *d_seek, uint64_t nsym, const hz_range *d_ranges, uint32_t nranges,
+                     uint8_t *d_out, uint64_t out_bytes, uint64_t *d_stats, uint32_t flags);
+
 /* Expand a seek table into the complete block index of the stream (start[] copied,
  * max_bits and sub[] computed, chains past the end as hz_pack writes them): byte for
  * byte what hz_pack / hz_index_build write. d_payload is the whole payload;
@@ -419,7 +458,13 @@ int hz_decode_host(const uint8_t *file, uint64_t len, uint8_t *out, uint64_t cap
  * are served by decoding the covering symbols, and the odd trailing byte of an
  * odd-sized original comes from the header. Only the header's codebook, the
  * range's seek entries and the span's payload bytes go to the device.
- * offset + count past the original's size: HZ_EINVAL. */
+ * offset + count past the original's size: HZ_EINVAL.
+ * hz_decode_ranges_host: nranges byte ranges [offsets[i], offsets[i] + counts[i])
+ * in one hz_decode_ranges call, their bytes concatenated in out in list order; one
+ * payload slice goes to the device, from the smallest byte_begin to the largest
+ * byte_end of the ranges' spans (whatever lies between them included). */
+int hz_decode_ranges_host(const uint8_t *file, uint64_t len, const uint64_t *seek, const uint64_t *offsets,
+                          const uint64_t *counts, uint32_t nranges, uint8_t *out);
 int hz_seek_build_host(const uint8_t *file, uint64_t len, uint64_t *seek, uint64_t cap_bytes, uint64_t *nsym);
 int hz_decode_range_host(const uint8_t *file, uint64_t len, const uint64_t *seek, uint64_t offset,
                          uint64_t count, uint8_t *out);

@@ -7,8 +7,12 @@
   d  hz_index_expand beside hz_index_build
   e  median and p95 latency of 50 seeded random ranges each of 4 KiB, 1 MiB and 64 MiB of output,
      from the seek table and with the full index
+  f  hz_decode_ranges (one call for the whole list, a wave per block) beside hz_decode_range (one call per
+     range), the two sides alternating in one loop and every result compared with the input: 50 random
+     4 KiB ranges and 50 of 1 MiB from the seek table and with the full index, one 4 KiB range from the seek
+     table; with stats[2], the most fix-up rounds any block of the run needed
 
-Prints one JSON line (and writes it to --out)."""
+--only f runs figure f alone. Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
 import os
@@ -36,7 +40,45 @@ def stats(xs):
     return {"min": round(xs[0], 4), "median": round(float(np.median(xs)), 4), "max": round(xs[-1], 4)}
 
 
-def case(c, n, reps):
+def batch_figures(c, x, payload, index, seek, nsym, reps):
+    """Figure f: (label, ranges, bytes each, modes)."""
+    res = {}
+    rng = np.random.default_rng(2)
+    for label, k, nbytes, modes in (("50x4KiB", 50, 4 << 10, (False, True)), ("1x4KiB", 1, 4 << 10, (False,)),
+                                    ("50x1MiB", 50, 1 << 20, (False, True))):
+        cnt = nbytes // 2
+        begins = [int(v) for v in rng.integers(0, nsym - cnt + 1, k)]
+        out = torch.empty(k * nbytes + 16, dtype=torch.uint8, device="cuda")
+        want = torch.cat([x[2 * b:2 * b + nbytes] for b in begins])
+        rg = torch.tensor([[b, cnt, i * nbytes] for i, b in enumerate(begins)], dtype=torch.int64, device="cuda")
+        st = torch.zeros(4, dtype=torch.int64, device="cuda")
+        for full in modes:
+            table = index if full else seek
+
+            def batch():
+                c.decode_ranges(payload, nsym, table, rg, out, stats=st, full_index=full)
+
+            def calls():
+                for i, b in enumerate(begins):
+                    c.decode_range(payload, nsym, table, b, cnt, out[i * nbytes:], full_index=full)
+
+            ta, tb, ok = [], [], True
+            for fn in (batch, calls):  # warm-up (also sizes the scratch)
+                timed(c, fn)
+            for _ in range(reps):      # alternating
+                for fn, ts in ((batch, ta), (calls, tb)):
+                    out.zero_()
+                    c.sync()
+                    ts.append(timed(c, fn))
+                    ok = ok and bool(torch.equal(out[:k * nbytes], want))
+            timed(c, batch)
+            res[f"f_{label}_{'full_index' if full else 'seek_table'}"] = {
+                "decode_ranges_ms": stats(ta), "decode_range_calls_ms": stats(tb), "all_equal_input": ok,
+                "batch_below_calls_in_every_repeat": max(ta) < min(tb), "stats": [int(v) for v in st.cpu()]}
+    return res
+
+
+def case(c, n, reps, only=""):
     x = torch.empty(n, dtype=torch.uint8, device="cuda")
     c.dev.generate(x.data_ptr(), n, offset=0, kind=1, alpha=1.1, seed=42)
     plan, payload, index = c.encode(x)
@@ -46,6 +88,10 @@ def case(c, n, reps):
     seek = index[:nb + 1].clone()
     out = torch.empty(n + 16, dtype=torch.uint8, device="cuda")
     res = {"bytes": n, "payload_bytes": (plan.start_bit + plan.payload_bits + 7) // 8}
+    if only == "f":
+        del out
+        res.update(batch_figures(c, x, payload, index, seek, nsym, reps))
+        return res
 
     def dec():
         c.decode(payload, nsym, index, out)
@@ -96,6 +142,8 @@ def case(c, n, reps):
             ok = bool(torch.equal(out[:nbytes], x[2 * begins[-1]:2 * begins[-1] + nbytes]))
             res[f"e_{label}_{mode}_ms"] = {"median": round(float(np.median(ts)), 4),
                                            "p95": round(float(np.percentile(ts, 95)), 4), "last_equals_input": ok}
+    del out
+    res.update(batch_figures(c, x, payload, index, seek, nsym, reps))
     return res
 
 
@@ -103,13 +151,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes-gib", type=int, nargs="*", default=[1, 16])
+    ap.add_argument("--only", default="", choices=["", "f"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     c = StreamCodec(0)
     res = {"tool": "range_timing", "build_id": _lib.build_id(), "reps": a.reps,
            "note": "ms, HIP events on the codec's stream around each call; a and b alternate in one loop"}
     for g in a.sizes_gib:
-        res[f"zipf_{g}GiB"] = case(c, g << 30, a.reps)
+        res[f"zipf_{g}GiB"] = case(c, g << 30, a.reps, a.only)
         torch.cuda.empty_cache()
     s = json.dumps(res)
     print(s)
