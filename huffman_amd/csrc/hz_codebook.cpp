@@ -1,5 +1,7 @@
 // hz_codebook.cpp -- host codebook, header bit-writer / parser and the device
-// table images (encode and decode) built from a codebook.
+// table images (encode and decode) built from a codebook, with the table plan that
+// decides which of them a codebook gets (build_enc_images, build_dec_images,
+// build_indexless_images: the uploads and tests/table_probe.cpp both go through it).
 //
 // The codebook follows the reference GPU encoder exactly:
 //   order : thrust::sequence + stable sort_by_key of (count, symbol)
@@ -9,6 +11,7 @@
 //           older than internals; pinned by oracle/generatecl_literal.py
 //   bits  : first child '1', second '0', root first (GenerateCW h:468-494 +
 //           toCpu h:562-574)
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -409,10 +412,7 @@ int build_dec_dense(const hz_codebook* cb, std::vector<uint32_t>& img, int& K) {
     K = (int)cb->max_len;
     const uint32_t ent = 1u << K;
     const uint32_t symwords = ent / 2 ? ent / 2 : 1;
-    const uint32_t lenwords = ent / 16 ? ent / 16 : 1;
-    uint32_t words = symwords + lenwords;
-    words = (words + 3) & ~3u;
-    img.assign(words, 0u);
+    img.assign(dense_dec_bytes((uint32_t)K) / 4, 0u);
     std::vector<uint8_t> seen(ent, 0);
     for (uint32_t s = 0; s < HZ_NSYM; ++s) {
         const uint32_t L = cb->len[s];
@@ -643,7 +643,30 @@ void build_walk_len(const hz_codebook* cb, std::vector<uint32_t>& img, std::vect
         if (plen[p]) put(p, plen[p] != 255 && plen[p] - bias <= 15 ? (uint32_t)(plen[p] - bias) : 0u);
 }
 
-}  // namespace hz
+// A byte table of code lengths per K-bit window, as the chain walker's two tables below are: `fill` where
+// no code starts; under a code of more than `skip` and at most K bits, its length; under a K-bit prefix of
+// longer codes, their length when they all have one, else 0. Padded with `fill_end` to whole uint4s.
+static void build_len_bytes(const hz_codebook* cb, int K, int skip, uint8_t fill, uint8_t fill_end,
+                            std::vector<uint32_t>& img) {
+    std::vector<uint8_t> t((size_t)1 << K, fill);
+    std::vector<uint8_t> plen((size_t)1 << K, 0);
+    for (uint32_t s = 0; s < HZ_NSYM; ++s) {
+        const int L = cb->len[s];
+        if (L <= skip) continue;
+        const uint64_t c = cb->code[s];
+        if (L <= K) {
+            memset(t.data() + (c << (K - L)), L, (size_t)1 << (K - L));
+        } else {
+            uint8_t& pl = plen[c >> (L - K)];
+            pl = pl == 0 || pl == (uint8_t)L ? (uint8_t)L : (uint8_t)255;
+        }
+    }
+    for (size_t p = 0; p < plen.size(); ++p)
+        if (plen[p]) t[p] = plen[p] != 255 ? plen[p] : 0;
+    while (t.size() % 16) t.push_back(fill_end);
+    img.assign(t.size() / 4, 0);
+    memcpy(img.data(), t.data(), t.size());
+}
 
 // The chain walker's length table (hz_chain.hip k_chain_walk): one BYTE per K-bit window, K =
 // min(max_len, 16) (2^16 bytes, the same 64 KiB of LDS as the 17-bit nibble table): the length of the
@@ -652,57 +675,102 @@ void build_walk_len(const hz_codebook* cb, std::vector<uint32_t>& img, std::vect
 // for prefixes shared by codes of different lengths. No bias and no nibble select per step, and
 // long lengths need no escape (16 GiB Zipf(1.1): escaped codewords 2.4 % -> 1.4 %). Windows no code
 // starts read min_len, so a walk past the stream's end keeps moving.
-namespace hz {
 void build_walk8(const hz_codebook* cb, std::vector<uint32_t>& img, int& K) {
-    const int M = (int)cb->max_len;
-    K = std::max(1, std::min(M, 16));
-    std::vector<uint8_t> t((size_t)1 << K, (uint8_t)cb->min_len);
-    std::vector<uint8_t> plen((size_t)1 << K, 0);
-    for (uint32_t s = 0; s < HZ_NSYM; ++s) {
-        const int L = cb->len[s];
-        if (!L) continue;
-        const uint64_t c = cb->code[s];
-        if (L <= K) {
-            const uint64_t w0 = c << (K - L), n = (uint64_t)1 << (K - L);
-            memset(t.data() + w0, L, (size_t)n);
-        } else {
-            uint8_t& pl = plen[c >> (L - K)];
-            pl = pl == 0 || pl == (uint8_t)L ? (uint8_t)L : (uint8_t)255;
-        }
-    }
-    for (size_t p = 0; p < plen.size(); ++p)
-        if (plen[p]) t[p] = plen[p] != 255 ? plen[p] : 0;
-    while (t.size() % 16) t.push_back(0);
-    img.assign(t.size() / 4, 0);
-    memcpy(img.data(), t.data(), t.size());
+    K = std::max(1, std::min((int)cb->max_len, 16));
+    build_len_bytes(cb, K, 0, (uint8_t)cb->min_len, 0, img);
 }
-}  // namespace hz
 
 // The chain walker's escape table for codebooks whose codes exceed kWalkMaxLen bits (build_walk_len's
 // 2^max_len table would not fit): one byte per M = kChainEscMaxBits window, the length of every code
 // longer than 16 bits (the byte table's escapes) that is at most M bits, or shared by every code under
 // the window when they are longer; 0 (a DEEP escape, resolved through the decode LUT) for M-bit
 // prefixes of codes of different lengths. Windows no code starts read 1.
-namespace hz {
 void build_chain_esc(const hz_codebook* cb, std::vector<uint32_t>& img, int& M) {
     M = std::min((int)cb->max_len, kChainEscMaxBits);
-    std::vector<uint8_t> t((size_t)1 << M, (uint8_t)1);
-    std::vector<uint8_t> plen((size_t)1 << M, 0);
-    for (uint32_t s = 0; s < HZ_NSYM; ++s) {
-        const int L = cb->len[s];
-        if (L <= 16) continue;
-        const uint64_t c = cb->code[s];
-        if (L <= M) {
-            memset(t.data() + (c << (M - L)), L, (size_t)1 << (M - L));
-        } else {
-            uint8_t& pl = plen[c >> (L - M)];
-            pl = pl == 0 || pl == (uint8_t)L ? (uint8_t)L : (uint8_t)255;
+    build_len_bytes(cb, M, 16, 1, 1, img);
+}
+
+// ---- The table plan: what the uploads stage and the table probe writes ----
+void build_enc_images(const hz_codebook* cb, EncImages& e) {
+    e = EncImages();
+    e.mode = select_enc_mode(cb);
+    // expected bits per symbol under the code's own distribution (Kraft weights 2^-L)
+    uint64_t nl[HZ_MAXLEN + 1] = {0};
+    for (uint32_t s = 0; s < HZ_NSYM; ++s) nl[cb->len[s]]++;
+    double avg = 0.0;
+    for (int L = 1; L <= HZ_MAXLEN; ++L) avg += ldexp((double)nl[L], -L) * L;
+    e.enc_avg_bits = avg > 0.0 ? avg : 1.0;
+    if (e.mode == ENC_FIXED16) {
+        e.lds = build_enc_fixed16(cb);
+        return;  // no count pass: no length tables
+    }
+    if (e.mode == ENC_DENSE) {
+        e.lds = build_enc_dense(cb);
+    } else if (e.mode == ENC_HOT) {
+        e.hot_mask = choose_hot_mask(cb);
+        e.lds = build_enc_hot(cb, e.hot_mask);
+        e.esc = build_enc_esc(cb, e.hot_mask);
+    } else {
+        e.wide = build_enc_wide(cb);
+    }
+    e.len8 = build_len8(cb);
+    e.lenpair = build_lenpair(cb);
+}
+
+// A decode image pair as the kernels take it: the LDS image in whole uint4s, the global levels never empty.
+static void pad_dec_images(std::vector<uint32_t>& lds, std::vector<uint32_t>& l2) {
+    while (lds.size() % 4) lds.push_back(0);
+    if (l2.empty()) l2.push_back(lut_leaf_entry(1, 0));
+}
+
+int build_dec_images(const hz_codebook* cb, DecImages& d) {
+    d = DecImages();
+    d.mode = select_dec_mode(cb);
+    int rc = HZ_OK;
+    if (d.mode == DEC_FIXED16) { d.lds = build_dec_fixed16(cb); d.k = 16; }
+    else if (d.mode == DEC_DENSE) rc = build_dec_dense(cb, d.lds, d.k);
+    else rc = build_dec_lut(cb, d.lds, d.l2, d.k, d.level_bits);
+    if (rc) return rc;
+    for (uint32_t s = 0; s < HZ_NSYM; ++s)
+        if (cb->len[s]) d.dec_avg_bits += ldexp((double)cb->len[s], -(int)cb->len[s]);
+    pad_dec_images(d.lds, d.l2);
+    if (d.mode != DEC_FIXED16 && d.lds.size() * 4 + 4 * dec_slot_words_max((int)cb->max_len) > kLdsBytes)
+        return HZ_ENOMEM;  // cannot happen for K1 <= 14 and codes <= 56 bits
+    return HZ_OK;
+}
+
+int build_indexless_images(const hz_codebook* cb, const DecImages& d, IndexlessImages& x) {
+    x = IndexlessImages();
+    if (d.mode == DEC_FIXED16 || cb->max_len < 1) return HZ_OK;  // FIXED16: positions are arithmetic
+    // the index walker's length tables
+    if (cb->max_len <= (uint32_t)kWalkMaxLen) {
+        build_walk_len(cb, x.walk_lds, x.walk_esc, x.walk_k, x.walk_m, x.walk_bias);
+        if (x.walk_lds.size() * 4 > (1u << kWalkK) / 2) {  // k_idx_walk's static table: no walker
+            x.walk_lds.clear();
+            x.walk_esc.clear();
+        } else if (x.walk_esc.empty()) {
+            x.walk_esc.push_back(0x01010101u);
         }
     }
-    for (size_t p = 0; p < plen.size(); ++p)
-        if (plen[p]) t[p] = plen[p] != 255 ? plen[p] : 0;
-    while (t.size() % 16) t.push_back(1);
-    img.assign(t.size() / 4, 0);
-    memcpy(img.data(), t.data(), t.size());
+    // the index-less chain decoder's tables: the byte length table, the escape table (the index walker's
+    // when it has one: codes <= kWalkMaxLen bits), LUT decode images
+    build_walk8(cb, x.walk8, x.walk8_k);
+    if (!x.walk_lds.empty()) x.chain_esc_m = x.walk_m;
+    else build_chain_esc(cb, x.chain_esc, x.chain_esc_m);
+    if (d.mode == DEC_LUT) {
+        x.chain_k = d.k;
+        x.chain_level_bits = d.level_bits;
+        return HZ_OK;
+    }
+    // DENSE: a LUT image beside the DENSE decoder's
+    const int rc = build_dec_lut(cb, x.chain_lds, x.chain_l2, x.chain_k, x.chain_level_bits);
+    if (rc) {
+        x.chain_lds.clear();
+        x.chain_l2.clear();
+        return rc;
+    }
+    pad_dec_images(x.chain_lds, x.chain_l2);
+    return HZ_OK;
 }
+
 }  // namespace hz

@@ -1,0 +1,336 @@
+// hz_image.cpp -- the whole-buffer flows behind hz_*_host (used by the tests and the Python package): a
+// complete .compressed image in host memory encoded, decoded, indexed and decoded by ranges on the
+// process-wide context, device work inside.
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+#include "hz_host.h"
+
+using namespace hz;
+
+namespace {
+
+struct EncodePlan {
+    std::unique_ptr<hz_codebook> cb{new hz_codebook()};
+    std::vector<uint64_t> hist = std::vector<uint64_t>(HZ_NSYM);
+    uint64_t header_bits = 0, payload_bits = 0;
+};
+
+// A host buffer to the process-wide context's device (din); histogram on the device, codebook on the host.
+int plan_encode(const uint8_t* in, uint64_t n, hz_ctx** ctx, DevBuf& din, EncodePlan& p) {
+    int rc = default_ctx(ctx);
+    if (rc) return rc;
+    hz_ctx* c = *ctx;
+    HZ_TRY(hipSetDevice(c->device));
+    if ((rc = din.alloc(n))) return rc;
+    if (n) HZ_TRY(hipMemcpyAsync(din.p, in, n, hipMemcpyHostToDevice, c->stream));
+    DevBuf dh;
+    if ((rc = dh.alloc(HZ_NSYM * 8))) return rc;
+    if ((rc = hz_hist16(c, (const uint8_t*)din.p, n, (uint64_t*)dh.p, 0))) return rc;
+    HZ_TRY(hipMemcpyAsync(p.hist.data(), dh.p, HZ_NSYM * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = hz_ctx_sync(c))) return rc;
+    if ((rc = hz_codebook_build(p.hist.data(), p.cb.get()))) return rc;
+    hz_header_bits(p.cb.get(), n, &p.header_bits);
+    hz_payload_bits(p.cb.get(), p.hist.data(), &p.payload_bits);
+    return HZ_OK;
+}
+
+// Encode a host buffer into a complete .compressed image.
+int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint32_t* nsym_out) {
+    hz_ctx* c;
+    DevBuf din;
+    EncodePlan p;
+    int rc = plan_encode(in, n, &c, din, p);
+    if (rc) return rc;
+    if (nsym_out) *nsym_out = p.cb->nsym;
+    const uint64_t hbytes_full = p.header_bits / 8;
+    const uint64_t total_bits = p.header_bits + p.payload_bits;
+    const uint64_t file_bytes = (total_bits + 7) / 8;
+    out.assign(file_bytes + 8, 0);
+    uint64_t hb;
+    uint32_t pend_bits;
+    uint8_t pend;
+    rc = hz_header_write(p.cb.get(), n, n & 1 ? in[n - 1] : 0, out.data(), out.size(), &hb, &pend_bits, &pend);
+    if (rc) return rc;
+    if (hb != hbytes_full) return HZ_EINVAL;
+    const uint64_t nsym = n / 2;
+    if (nsym > 0) {
+        if ((rc = hz_codebook_upload(c, p.cb.get()))) return rc;
+        const uint64_t start_bit = pend_bits;
+        const uint64_t pay_bytes = file_bytes - hbytes_full;
+        const uint64_t words = (start_bit + p.payload_bits + 31) / 32;
+        DevBuf dout;
+        if ((rc = dout.alloc(words * 4))) return rc;
+        if ((rc = hz_pack(c, (const uint8_t*)din.p, n, start_bit, (uint32_t)(pend >> (8 - pend_bits)) * (pend_bits ? 1 : 0),
+                          (uint8_t*)dout.p, words * 4, nullptr)))
+            return rc;
+        HZ_TRY(hipMemcpyAsync(out.data() + hbytes_full, dout.p, pay_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+    } else if (pend_bits) {
+        out[hbytes_full] = pend;  // unreachable (header is byte aligned without symbols) but kept exact
+    }
+    out.resize(file_bytes);
+    return HZ_OK;
+}
+
+// A complete .compressed image in host memory, opened: the header parsed, the payload located.
+struct OpenedImage {
+    const uint8_t* f = nullptr;
+    std::unique_ptr<hz_codebook> cb{new hz_codebook()};
+    hz_header_info info;
+    uint64_t nsym = 0;  // symbols
+    uint64_t pay = 0;   // payload bytes: from info.payload_byte to the end of the file
+
+    int open(const uint8_t* file, uint64_t len) {
+        const int rc = hz_header_parse(file, len, cb.get(), &info);
+        if (rc) return rc;
+        f = file;
+        nsym = info.n / 2;
+        pay = len - info.payload_byte;
+        return HZ_OK;
+    }
+    // every codeword is >= min_len bits: a header claiming more symbols than the
+    // payload can hold is malformed (checked before anything is allocated)
+    bool holds_its_symbols() const {
+        const uint64_t pay_bits = pay * 8 > info.payload_bit ? pay * 8 - info.payload_bit : 0;
+        return nsym <= pay_bits / std::max<uint32_t>(cb->min_len, 1);
+    }
+    // payload bytes [b, e) to the device, with 16 zero bytes behind them
+    int upload(hz_ctx* c, uint64_t b, uint64_t e, DevBuf& d) const {
+        const int rc = d.alloc(e - b + 16);
+        if (rc) return rc;
+        HZ_TRY(hipMemsetAsync(d.p, 0, e - b + 16, c->stream));
+        HZ_TRY(hipMemcpyAsync(d.p, f + info.payload_byte + b, e - b, hipMemcpyHostToDevice, c->stream));
+        return HZ_OK;
+    }
+};
+
+// Entries b0 .. b1 + 1 of a seek table to the device. The device reads those entries only, addressed
+// from entry 0: *d_seek0 is where entry 0 would stand.
+int upload_seek_slice(hz_ctx* c, const uint64_t* seek, uint64_t b0, uint64_t b1, DevBuf& d, const uint64_t** d_seek0) {
+    const int rc = d.alloc(8 * (b1 - b0 + 2));
+    if (rc) return rc;
+    HZ_TRY(hipMemcpyAsync(d.p, seek + b0, 8 * (b1 - b0 + 2), hipMemcpyHostToDevice, c->stream));
+    *d_seek0 = (const uint64_t*)d.p - b0;
+    return HZ_OK;
+}
+
+// Decode a complete .compressed image.
+int decode_image(const uint8_t* f, uint64_t len, std::vector<uint8_t>& out) {
+    OpenedImage im;
+    int rc = im.open(f, len);
+    if (rc) return rc;
+    if (!im.holds_its_symbols()) return HZ_EFORMAT;
+    try {
+        out.assign(2 * im.nsym + (im.info.is_odd ? 1 : 0), 0);
+    } catch (const std::bad_alloc&) {
+        return HZ_ENOMEM;
+    }
+    if (im.nsym > 0) {
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload(c, im.cb.get()))) return rc;
+        DevBuf dpay, didx, dout;
+        if ((rc = im.upload(c, 0, im.pay, dpay))) return rc;
+        if ((rc = didx.alloc(16))) return rc;
+        if ((rc = dout.alloc(2 * im.nsym + 16))) return rc;
+        // index-less decode (no block index); a payload with fewer than nsym codewords (truncated
+        // or corrupt file) ends past the payload: rejected
+        if ((rc = hz_decode_indexless(c, (const uint8_t*)dpay.p, im.pay, im.info.payload_bit, im.nsym, (uint8_t*)dout.p,
+                                      (uint64_t*)didx.p)))
+            return rc;
+        uint64_t end_bit = 0;
+        HZ_TRY(hipMemcpyAsync(&end_bit, didx.p, 8, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+        if (end_bit > im.pay * 8) return HZ_EFORMAT;
+        HZ_TRY(hipMemcpyAsync(out.data(), dout.p, 2 * im.nsym, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+    }
+    if (im.info.is_odd) out[2 * im.nsym] = (uint8_t)im.info.last_byte;
+    return HZ_OK;
+}
+
+// The seek table of a complete .compressed image: hz_index_build's start[].
+int seek_build_image(const uint8_t* f, uint64_t len, uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym_out) {
+    OpenedImage im;
+    int rc = im.open(f, len);
+    if (rc) return rc;
+    *nsym_out = im.nsym;
+    if (im.nsym == 0) return HZ_OK;
+    if (!im.holds_its_symbols()) return HZ_EFORMAT;
+    if (!seek || cap_bytes < hz_seek_bytes(im.nsym)) return HZ_ECAP;
+    hz_ctx* c;
+    if ((rc = default_ctx(&c))) return rc;
+    HZ_TRY(hipSetDevice(c->device));
+    if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
+    DevBuf dpay, didx;
+    if ((rc = im.upload(c, 0, im.pay, dpay))) return rc;
+    if ((rc = didx.alloc(hz_index_bytes(im.nsym)))) return rc;
+    if ((rc = hz_index_build(c, (const uint8_t*)dpay.p, im.pay, im.info.payload_bit, im.nsym, (uint64_t*)didx.p))) return rc;
+    HZ_TRY(hipMemcpyAsync(seek, didx.p, hz_seek_bytes(im.nsym), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = hz_ctx_sync(c))) return rc;
+    if (seek[index_blocks(im.nsym)] > im.pay * 8) return HZ_EFORMAT;  // fewer than nsym codewords in the payload
+    return HZ_OK;
+}
+
+// Bytes [offset, offset + count) of the original of a complete .compressed image, from its seek table.
+int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uint64_t offset, uint64_t count,
+                       uint8_t* out) {
+    OpenedImage im;
+    int rc = im.open(f, len);
+    if (rc) return rc;
+    if (offset > im.info.n || count > im.info.n - offset) return HZ_EINVAL;
+    if (count == 0) return HZ_OK;
+    if (!out) return HZ_EINVAL;
+    const uint64_t s0 = offset / 2, s1 = std::min((offset + count + 1) / 2, im.nsym);  // covering symbols
+    if (s1 > s0) {
+        if (!seek) return HZ_EINVAL;
+        uint64_t bb, be;
+        if ((rc = hz_seek_span(seek, im.nsym, s0, s1 - s0, &bb, &be))) return rc;
+        if (bb >= im.pay) return HZ_EFORMAT;
+        be = std::min(be, im.pay);
+        const uint64_t b0 = s0 / kBlockSyms, b1 = (s1 - 1) / kBlockSyms;
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
+        DevBuf dpay, dseek, dout;
+        const uint64_t* d_seek0;
+        if ((rc = im.upload(c, bb, be, dpay))) return rc;
+        if ((rc = upload_seek_slice(c, seek, b0, b1, dseek, &d_seek0))) return rc;
+        if ((rc = dout.alloc(2 * (s1 - s0)))) return rc;
+        if ((rc = hz_decode_range(c, (const uint8_t*)dpay.p, be - bb, bb, d_seek0, im.nsym, s0, s1 - s0, (uint8_t*)dout.p, 0)))
+            return rc;
+        std::vector<uint8_t> tmp(2 * (s1 - s0));
+        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp.size(), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+        const uint64_t skip = offset - 2 * s0;
+        memcpy(out, tmp.data() + skip, std::min<uint64_t>(count, tmp.size() - skip));
+    }
+    if (im.info.is_odd && offset + count == im.info.n) out[count - 1] = (uint8_t)im.info.last_byte;
+    return HZ_OK;
+}
+
+// Byte ranges [offsets[i], offsets[i] + counts[i]) of the original, concatenated in `out`: one
+// hz_decode_ranges call over one payload slice (the smallest byte_begin to the largest byte_end).
+int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
+                        const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    OpenedImage im;
+    int rc = im.open(f, len);
+    if (rc) return rc;
+    if (nranges == 0) return HZ_OK;
+    if (!offsets || !counts) return HZ_EINVAL;
+    std::vector<hz_range> rg(nranges);
+    uint64_t tmp_bytes = 0, total = 0, bb = UINT64_MAX, be = 0, b0 = UINT64_MAX, b1 = 0;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (offsets[i] > im.info.n || counts[i] > im.info.n - offsets[i]) return HZ_EINVAL;
+        const uint64_t s0 = offsets[i] / 2, s1 = std::min((offsets[i] + counts[i] + 1) / 2, im.nsym);  // covering symbols
+        rg[i].sym_begin = s0;
+        rg[i].sym_count = counts[i] && s1 > s0 ? s1 - s0 : 0;
+        rg[i].out_byte = tmp_bytes;
+        tmp_bytes += 2 * rg[i].sym_count;
+        total += counts[i];
+        if (rg[i].sym_count) {
+            if (!seek) return HZ_EINVAL;
+            uint64_t rb, re;
+            if ((rc = hz_seek_span(seek, im.nsym, s0, rg[i].sym_count, &rb, &re))) return rc;
+            bb = std::min(bb, rb);
+            be = std::max(be, re);
+            b0 = std::min(b0, s0 / kBlockSyms);
+            b1 = std::max(b1, (s1 - 1) / kBlockSyms);
+        }
+    }
+    if (total && !out) return HZ_EINVAL;
+    std::vector<uint8_t> tmp(tmp_bytes);
+    if (tmp_bytes) {
+        if (bb >= im.pay) return HZ_EFORMAT;
+        be = std::min(be, im.pay);
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
+        DevBuf dpay, dseek, drg, dout;
+        const uint64_t* d_seek0;
+        if ((rc = im.upload(c, bb, be, dpay))) return rc;
+        if ((rc = upload_seek_slice(c, seek, b0, b1, dseek, &d_seek0))) return rc;
+        if ((rc = drg.alloc(sizeof(hz_range) * (uint64_t)nranges))) return rc;
+        HZ_TRY(hipMemcpyAsync(drg.p, rg.data(), sizeof(hz_range) * (uint64_t)nranges, hipMemcpyHostToDevice, c->stream));
+        if ((rc = dout.alloc(tmp_bytes))) return rc;
+        if ((rc = hz_decode_ranges(c, (const uint8_t*)dpay.p, be - bb, bb, d_seek0, im.nsym, (const hz_range*)drg.p, nranges,
+                                   (uint8_t*)dout.p, tmp_bytes, nullptr, 0)))
+            return rc;
+        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;
+    }
+    uint8_t* o = out;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (!counts[i]) continue;
+        const uint64_t skip = offsets[i] - 2 * rg[i].sym_begin, have = 2 * rg[i].sym_count;
+        if (have > skip) memcpy(o, tmp.data() + rg[i].out_byte + skip, std::min<uint64_t>(counts[i], have - skip));
+        if (im.info.is_odd && offsets[i] + counts[i] == im.info.n) o[counts[i] - 1] = (uint8_t)im.info.last_byte;
+        o += counts[i];
+    }
+    return HZ_OK;
+}
+
+}  // namespace
+
+// A flow's result to the caller's buffer: its size always, its bytes when they fit.
+static int give(const std::vector<uint8_t>& v, uint8_t* out, uint64_t cap, uint64_t* len) {
+    *len = v.size();
+    if (cap < v.size() || (!out && v.size())) return HZ_ECAP;
+    if (v.size()) memcpy(out, v.data(), v.size());
+    return HZ_OK;
+}
+
+extern "C" int hz_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len) {
+    if ((!in && n) || !out_len) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> img;  // (never empty: the header alone is 11 bytes)
+        const int rc = encode_image(in, n, img, nullptr);
+        return rc ? rc : give(img, out, cap, out_len);
+    });
+}
+
+extern "C" int hz_encoded_size(const uint8_t* in, uint64_t n, uint64_t* out_len) {
+    if ((!in && n) || !out_len) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        hz_ctx* c;
+        DevBuf din;
+        EncodePlan p;
+        const int rc = plan_encode(in, n, &c, din, p);
+        if (!rc) *out_len = (p.header_bits + p.payload_bits + 7) / 8;
+        return rc;
+    });
+}
+
+extern "C" int hz_decode_host(const uint8_t* file, uint64_t len, uint8_t* out, uint64_t cap, uint64_t* out_n) {
+    if (!file || !out_n) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> dec;
+        const int rc = decode_image(file, len, dec);
+        return rc ? rc : give(dec, out, cap, out_n);
+    });
+}
+
+extern "C" int hz_seek_build_host(const uint8_t* file, uint64_t len, uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym) {
+    if (!file || !nsym) return HZ_EINVAL;
+    return guarded([&] { return seek_build_image(file, len, seek, cap_bytes, nsym); });
+}
+
+extern "C" int hz_decode_range_host(const uint8_t* file, uint64_t len, const uint64_t* seek, uint64_t offset,
+                                    uint64_t count, uint8_t* out) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&] { return decode_range_image(file, len, seek, offset, count, out); });
+}
+
+extern "C" int hz_decode_ranges_host(const uint8_t* file, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
+                                     const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&] { return decode_ranges_image(file, len, seek, offsets, counts, nranges, out); });
+}

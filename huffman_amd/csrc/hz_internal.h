@@ -1,6 +1,6 @@
-// hz_internal.h -- shared layout constants and launch interfaces between the
-// host side (hz_host.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip, hz_decode.hip, hz_ranges.hip,
-// hz_index.hip, hz_chain.hip, hz_codebook_gpu.hip; DESIGN.md "Source layout").
+// hz_internal.h -- shared layout constants, the table plan and launch interfaces between the host side
+// (hz_host.cpp, hz_image.cpp, hz_stream.cpp, hz_codebook.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip,
+// hz_decode.hip, hz_ranges.hip, hz_index.hip, hz_chain.hip, hz_codebook_gpu.hip; DESIGN.md "Source layout").
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -248,8 +248,42 @@ __host__ __device__ inline uint32_t hot_slot(uint32_t s, uint32_t m) { return (s
 // (the first byte alone would pick the bank; skewed data keeps it small).
 __host__ __device__ inline uint32_t hot_word(uint32_t slot) { return slot ^ ((slot >> 8) & 0x3fu); }
 
-// Host builders of the table images (hz_codebook.cpp): the mode a codebook takes, and every image the
-// uploads (hz_host.cpp) and the table probe (tests/table_probe.cpp) build from it.
+// The table plan (hz_codebook.cpp, free of HIP calls): everything a codebook gets on the device -- the
+// modes, which images exist, their padding and fillers, what shares a table. The uploads (hz_host.cpp)
+// stage what it returns and the table probe (tests/table_probe.cpp) writes it to a file, so the images
+// the CPU tests check entry by entry are built through the uploads' own plan. An image is empty where
+// the codebook has none.
+struct EncImages {
+    int mode = -1;                  // EncMode
+    uint32_t hot_mask = 0x8000;     // HOT only
+    double enc_avg_bits = 16.0;     // Kraft estimate of bits per symbol: sum 2^-L * L
+    std::vector<uint32_t> lds;      // FIXED16, DENSE, HOT: the pack kernel's LDS image
+    std::vector<uint32_t> esc;      // HOT: escapes
+    std::vector<uint64_t> wide;     // WIDE
+    std::vector<uint32_t> len8, lenpair;  // every mode but FIXED16
+};
+struct DecImages {
+    int mode = -1;                  // DecMode
+    int k = 0, level_bits = 0;      // level_bits: LUT only
+    double dec_avg_bits = 0.0;      // Kraft estimate of bits per codeword (sizes the index-less decoder's records)
+    std::vector<uint32_t> lds;      // padded to whole uint4s
+    std::vector<uint32_t> l2;       // never empty: lut_leaf_entry(1, 0) where the mode has no global level
+};
+struct IndexlessImages {
+    std::vector<uint32_t> walk_lds, walk_esc;  // empty: no walker tables (the segment walkers build the index)
+    int walk_k = 0, walk_m = 0, walk_bias = 0;
+    std::vector<uint32_t> walk8;    // every mode but FIXED16, with the chain tables below
+    int walk8_k = 0;
+    std::vector<uint32_t> chain_esc;  // empty beside a walker: the chain decoder reads walk_esc
+    int chain_esc_m = 0;
+    std::vector<uint32_t> chain_lds, chain_l2;  // DENSE: a LUT beside the decode table (LUT: the decode tables)
+    int chain_k = 0, chain_level_bits = 0;
+};
+void build_enc_images(const hz_codebook* cb, EncImages& e);
+int build_dec_images(const hz_codebook* cb, DecImages& d);  // HZ_ENOMEM: the image leaves a worst-case block no LDS
+// after build_dec_images of the same codebook (the uploads flush the decode set in between)
+int build_indexless_images(const hz_codebook* cb, const DecImages& d, IndexlessImages& x);
+// The plan's parts: the mode a codebook takes and the builder of each image.
 int select_enc_mode(const hz_codebook* cb);
 std::vector<uint32_t> build_enc_dense(const hz_codebook* cb);
 std::vector<uint32_t> build_enc_fixed16(const hz_codebook* cb);

@@ -1,6 +1,8 @@
-// table_probe.cpp -- the device table images of a codebook, built on the host exactly as the uploads
-// (hz_host.cpp hz_codebook_upload_encode_impl / hz_codebook_upload_decode_impl) decide to, written to a
-// file for tests/test_table_images.py to check entry by entry against tests/table_model.py.
+// table_probe.cpp -- the device table images of a codebook, built on the host through the uploads' own
+// plan (hz_codebook.cpp build_enc_images / build_dec_images / build_indexless_images, which hz_host.cpp's
+// hz_codebook_upload_encode / hz_codebook_upload_decode stage), written to a file for
+// tests/test_table_images.py to check entry by entry against tests/table_model.py. It decides nothing
+// itself: it names the sections and writes what the plan returns.
 // A stand-alone host program: no HIP call, no GPU code; it links hz_codebook.cpp only.
 //
 // Build (from the repository root):
@@ -56,84 +58,43 @@ void section(FILE* f, const char* name, const Params& params, const std::vector<
 
 const std::vector<uint32_t> kNone;
 
-// hz_codebook_upload_encode_impl
+// What hz_codebook_upload_encode stages.
 void probe_encode(FILE* f, const hz_codebook* cb) {
-    const int mode = select_enc_mode(cb);
-    section(f, "enc", {{"mode", mode}}, kNone);
-    if (mode == ENC_FIXED16) {
-        section(f, "enc_fixed16", {}, build_enc_fixed16(cb));
-    } else if (mode == ENC_DENSE) {
-        section(f, "enc_dense", {}, build_enc_dense(cb));
-    } else if (mode == ENC_HOT) {
-        const uint32_t mask = choose_hot_mask(cb);
-        section(f, "enc_hot", {{"mask", mask}}, build_enc_hot(cb, mask));
-        section(f, "enc_esc", {{"mask", mask}}, build_enc_esc(cb, mask));
-    }
-    if (mode == ENC_WIDE) section(f, "enc_wide", {}, build_enc_wide(cb));
-    if (mode != ENC_FIXED16) {
-        section(f, "len8", {}, build_len8(cb));
-        section(f, "lenpair", {}, build_lenpair(cb));
-    }
+    EncImages e;
+    build_enc_images(cb, e);
+    section(f, "enc", {{"mode", e.mode}}, kNone);
+    // an image exists where it is not empty; the mode only names the LDS image
+    const char* names[] = {"enc_dense", "enc_hot", "enc_wide", "enc_fixed16"};
+    const Params mask = e.esc.empty() ? Params{} : Params{{"mask", e.hot_mask}};  // the pair that shares it
+    if (!e.lds.empty()) section(f, names[e.mode], mask, e.lds);
+    if (!e.esc.empty()) section(f, "enc_esc", mask, e.esc);
+    if (!e.wide.empty()) section(f, "enc_wide", {}, e.wide);
+    if (!e.len8.empty()) section(f, "len8", {}, e.len8);
+    if (!e.lenpair.empty()) section(f, "lenpair", {}, e.lenpair);
 }
 
-// hz_codebook_upload_decode_impl
+// What hz_codebook_upload_decode stages: the decode set, then the index-less set.
 void probe_decode(FILE* f, const hz_codebook* cb) {
-    const int mode = select_dec_mode(cb);
-    std::vector<uint32_t> dimg, l2, wimg, wesc;
-    int k = 0, lvl = 0, rc = HZ_OK;
-    if (mode == DEC_FIXED16) { dimg = build_dec_fixed16(cb); k = 16; }
-    else if (mode == DEC_DENSE) rc = build_dec_dense(cb, dimg, k);
-    else rc = build_dec_lut(cb, dimg, l2, k, lvl);
-    if (!rc) {
-        while (dimg.size() % 4) dimg.push_back(0);
-        if (mode != DEC_FIXED16 && dimg.size() * 4 + 4 * dec_slot_words_max((int)cb->max_len) > kLdsBytes) rc = HZ_ENOMEM;
-    }
-    section(f, "dec", {{"mode", mode}, {"rc", rc}}, kNone);
+    DecImages d;
+    const int rc = build_dec_images(cb, d);
+    section(f, "dec", {{"mode", d.mode}, {"rc", rc}}, kNone);
     if (rc) return;
-    if (l2.empty()) l2.push_back(lut_leaf_entry(1, 0));
     const char* names[] = {"dec_dense", "dec_lut", "dec_fixed16"};
-    section(f, names[mode], {{"k", k}, {"lvl", lvl}}, dimg);
-    section(f, "dec_l2", {}, l2);
-    bool walker = false;
-    int walk_m = 0;
-    if (mode != DEC_FIXED16 && cb->max_len >= 1 && cb->max_len <= (uint32_t)kWalkMaxLen) {
-        int wk = 0, wm = 0, bias = 0;
-        build_walk_len(cb, wimg, wesc, wk, wm, bias);
-        if (wimg.size() * 4 <= (1u << kWalkK) / 2) {
-            if (wesc.empty()) wesc.push_back(0x01010101u);
-            section(f, "walk_len", {{"k", wk}, {"m", wm}, {"bias", bias}}, wimg);
-            section(f, "walk_esc", {{"m", wm}}, wesc);
-            walker = true;
-            walk_m = wm;
-        }
+    section(f, names[d.mode], {{"k", d.k}, {"lvl", d.level_bits}}, d.lds);
+    section(f, "dec_l2", {}, d.l2);
+    IndexlessImages x;
+    const int crc = build_indexless_images(cb, d, x);
+    if (!x.walk_lds.empty()) {
+        section(f, "walk_len", {{"k", x.walk_k}, {"m", x.walk_m}, {"bias", x.walk_bias}}, x.walk_lds);
+        section(f, "walk_esc", {{"m", x.walk_m}}, x.walk_esc);
     }
-    if (mode != DEC_FIXED16 && cb->max_len >= 1) {
-        std::vector<uint32_t> w8;
-        int k8 = 0;
-        build_walk8(cb, w8, k8);
-        section(f, "walk8", {{"k", k8}}, w8);
-        if (walker) {
-            section(f, "chain_esc", {{"m", walk_m}, {"shared", 1}}, kNone);  // the index walker's table
-        } else {
-            std::vector<uint32_t> cesc;
-            int m = 0;
-            build_chain_esc(cb, cesc, m);
-            section(f, "chain_esc", {{"m", m}, {"shared", 0}}, cesc);
-        }
-        if (mode != DEC_LUT) {  // DENSE: a LUT image beside the DENSE decoder's
-            std::vector<uint32_t> cimg, cl2;
-            int ck = 0, clvl = 0;
-            const int crc = build_dec_lut(cb, cimg, cl2, ck, clvl);
-            if (!crc) {
-                while (cimg.size() % 4) cimg.push_back(0);
-                if (cl2.empty()) cl2.push_back(lut_leaf_entry(1, 0));
-            } else {
-                cimg.clear();
-                cl2.clear();
-            }
-            section(f, "chain_lut", {{"k", ck}, {"lvl", clvl}, {"rc", crc}}, cimg);
-            section(f, "chain_l2", {}, cl2);
-        }
+    if (x.walk8.empty()) return;  // FIXED16: no index-less tables
+    section(f, "walk8", {{"k", x.walk8_k}}, x.walk8);
+    // shared: the index walker's table, no words here
+    section(f, "chain_esc", {{"m", x.chain_esc_m}, {"shared", x.chain_esc.empty()}}, x.chain_esc);
+    if (!x.chain_lds.empty() || crc) {  // DENSE: a LUT image beside the DENSE decoder's (or its failure)
+        section(f, "chain_lut", {{"k", x.chain_k}, {"lvl", x.chain_level_bits}, {"rc", crc}}, x.chain_lds);
+        section(f, "chain_l2", {}, x.chain_l2);
     }
 }
 

@@ -7,6 +7,8 @@ chosen for their lengths reach what natural data reaches only at tens of gigabyt
 2048 x 56 bits (the largest decode slot), blocks past 65 536 bits in every consumer
 (dec_chain_offsets' rebuild), 35..56-bit codes through the index-less walk, the pack's slot overflow,
 cold list and direct path, chains past the stream's end, and prefix codes that never resynchronise.
+One test walks every ordered pair of the five table classes on one context (what a re-upload must
+reset or re-alias), not left to the order of the cases.
 
 Every device result is compared with the model (never only with another device result); every
 output and index buffer sits between 64-byte guards of 0xA5. A device-side status at hz_ctx_sync
@@ -406,6 +408,82 @@ def _parts(ck, codec, bk, m, pay, want, bounds, slices):
 @pytest.mark.parametrize("case", CASES, ids=_case_id)
 def test_designed_stream(codec, case):
     failed = run_case(codec, case)
+    assert not failed, "\n".join(failed)
+
+
+TOUR_CLASSES = ["hot25", "fib57", "dense16", "fixed16", "zipf21"]
+TOUR_NSYM = 3 * BLK + 5     # three blocks and a ragged tail: the least that has a middle block
+
+
+def _tour(n):
+    """A closed walk over every ordered pair of n classes (n prime): for each step d = 1 .. n - 1 the
+    cycle 0, d, 2d, ... (mod n) back to 0 takes the n pairs (i, i + d) once."""
+    walk = [0]
+    for d in range(1, n):
+        walk += [(d * k) % n for k in range(1, n + 1)]
+    return walk
+
+
+def test_reupload_between_table_classes(codec):
+    """Every ordered pair of table classes uploaded one after the other on ONE context: hot25 (LUT with
+    walker tables, HOT encode), fib57 (codes past kWalkMaxLen: no walker, its own chain escape table,
+    WIDE encode), dense16 (DENSE with its chain LUT beside), fixed16 (no index-less tables at all) and
+    zipf21 (a full alphabet). A closed tour of the 20 pairs takes 21 uploads; after each one a `chains`
+    stream of three blocks and a ragged tail is packed at a nonzero start bit and goes through hz_decode,
+    hz_decode_indexless and hz_index_build, each bit-exact against the model with its guards intact. A
+    re-upload that leaves behind what the previous class set -- walk_lds_bytes, the chain_* views, the
+    FIXED16 part state, a table smaller than its capacity -- decodes through the wrong tables here."""
+    import torch
+    dev = codec.dev
+    walk = _tour(len(TOUR_CLASSES))
+    pairs = set(zip(walk, walk[1:]))
+    assert len(walk) == 21 and walk[0] == walk[-1]
+    assert pairs == {(i, j) for i in range(5) for j in range(5) if i != j}
+    models = {}
+    failed = []
+    for step, ci in enumerate(walk):
+        bk = book(TOUR_CLASSES[ci])
+        if ci not in models:
+            start_bit = START_BITS[1 + ci % 4]      # 5, 31, 32 or 45: never 0
+            rng = np.random.default_rng(zlib.crc32(("tour-" + bk.name).encode()))
+            sym = _stream(bk, "chains", TOUR_NSYM, rng)
+            models[ci] = (sym, ref_stream.model(sym, bk.ln, bk.code, start_bit, _lead(start_bit)))
+        sym, m = models[ci]
+        nsym, start_bit, nbytes, ibytes = TOUR_NSYM, m.start_bit, m.payload.size, m.index.size
+        first = 4 * (start_bit // 32)
+        tag = "upload %d (%s after %s)" % (step, bk.name, TOUR_CLASSES[walk[step - 1]] if step else "-")
+        ck = Checks(codec)
+        dev.upload(bk.cb)
+        _uploaded[0] = (id(codec), bk.name)
+        x = torch.from_numpy(sym.view(np.uint8)).cuda()
+        want = torch.from_numpy(sym.view(np.uint8).copy()).cuda()
+        model_index = torch.from_numpy(m.index).cuda()
+        paybuf, pay = _guarded(nbytes)
+        idxbuf, idx = _guarded(ibytes)
+        ck.run("pack", lambda: dev.pack(x.data_ptr(), x.numel(), start_bit, m.lead, pay.data_ptr(), nbytes, idx.data_ptr()))
+        ck.expect("pack payload", np.array_equal(_host(pay)[first:], m.payload[first:]))
+        ck.expect("pack index", np.array_equal(_host(idx), m.index), _index_diff(_host(idx), m, nsym))
+        ck.expect("pack guards", _guards_intact(paybuf, nbytes) and _guards_intact(idxbuf, ibytes))
+        # the consumers read the MODEL's payload and index
+        paybuf, pay = _guarded(nbytes)
+        pay.copy_(torch.from_numpy(m.payload))
+        obuf, out = _guarded(2 * nsym)
+        ck.run("decode", lambda: dev.decode(pay.data_ptr(), nbytes, nsym, model_index.data_ptr(), out.data_ptr()))
+        ck.expect("decode", torch.equal(out, want))
+        ck.expect("decode guards", _guards_intact(obuf, 2 * nsym))
+        obuf, out = _guarded(2 * nsym)
+        end = torch.full((8,), 0xA5, dtype=torch.uint8, device="cuda")
+        ck.run("indexless", lambda: dev.decode_indexless(pay.data_ptr(), nbytes, start_bit, nsym, out.data_ptr(),
+                                                         end.data_ptr()))
+        ck.expect("indexless symbols", torch.equal(out, want))
+        ck.expect("indexless end bit", _u64(end)[0] == m.end_bit, f"{_u64(end)[0]} != {m.end_bit}")
+        ck.expect("indexless guards", _guards_intact(obuf, 2 * nsym))
+        i3buf, i3 = _guarded(ibytes)
+        ck.run("index_build", lambda: dev.index_build(pay.data_ptr(), nbytes, start_bit, nsym, i3.data_ptr()))
+        ck.expect("index_build", np.array_equal(_host(i3), m.index), _index_diff(_host(i3), m, nsym))
+        ck.expect("index_build guards", _guards_intact(i3buf, ibytes))
+        ck.expect("payload (an input) changed", np.array_equal(_host(pay), m.payload) and _guards_intact(paybuf, nbytes))
+        failed += [tag + ": " + f for f in ck.failed]
     assert not failed, "\n".join(failed)
 
 
