@@ -111,6 +111,11 @@ PROTOTYPES = [
     ("hz_indexless_scan", _I, [_P, _P, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _P]),
     ("hz_indexless_refix", _I, [_P, _U64, _P]),
     ("hz_indexless_decode", _I, [_P, _U64, _P, _P]),
+    ("hz_seek_build", _I, [_P, _P, _U64, _U64, _U64, _P]),
+    ("hz_decode_indexless_seek", _I, [_P, _P, _U64, _U64, _U64, _P, _P, _U64, _U64, _U64, _P]),
+    ("hz_indexless_seek", _I, [_P, _U64, _U64, _U64, _P]),
+    ("hz_extract_stream_seek", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_decode_range_file", _I, [ctypes.c_char_p, _P, _U64, _U64, _P]),
     ("hz_last_kernel_ms", _I, [_P, _I, ctypes.POINTER(ctypes.c_float)]),
     ("hz_generate", _I, [_P, _P, _U64, _U64, _I, ctypes.c_double, _U64]),
     ("hz_archive_file", _I, [ctypes.c_char_p, _I]),

@@ -11,6 +11,7 @@ encodeFromCW -> pack, translateFile -> decode). Every call goes to the gfx950
 kernels of libhuffman_amd.so.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -185,6 +186,45 @@ def decode_range(blob, seek, offset, length):
     return out[:length].tobytes()
 
 
+def seek_entries(nsym):
+    """The codeword every seek entry points at: s_b = min(2048 b, nsym) for b = 0 .. nblocks(nsym); the
+    last one is the stream's end. Empty for nsym 0 (seek_bytes(0) == 0)."""
+    stride = 2048
+    if nsym == 0:
+        return []
+    nb = (nsym + stride - 1) // stride
+    return [min(stride * b, nsym) for b in range(nb + 1)]
+
+
+def build_seek_file(path, window_bytes=256 << 20, out_path=None):
+    """The seek table of a .compressed file on disk (uint64 start[nblocks + 1], as build_seek counts),
+    streamed through windows of window_bytes of payload: host memory is two windows and the table,
+    whatever the file's size. With out_path the file is extracted there in the same pass; without it
+    nothing is decoded (hz_extract_stream_seek)."""
+    lib = load()
+    src = os.fsencode(path)
+    dst = os.fsencode(out_path) if out_path is not None else None
+    nsym = ctypes.c_uint64()
+    rc = lib.hz_extract_stream_seek(src, None, window_bytes, 0, None, 0, ctypes.byref(nsym))  # the size: HZ_ECAP
+    if rc not in (0, -6):
+        check(rc, "hz_extract_stream_seek")
+    seek = np.zeros(max(seek_bytes(nsym.value) // 8, 1), dtype=np.uint64)
+    check(lib.hz_extract_stream_seek(src, dst, window_bytes, 0, seek.ctypes.data_as(ctypes.c_void_p), seek.size * 8,
+                                     ctypes.byref(nsym)), "hz_extract_stream_seek")
+    return seek[:seek_bytes(nsym.value) // 8]
+
+
+def decode_range_file(path, seek, offset, length):
+    """Bytes [offset, offset + length) of the original from a .compressed file on disk and its seek
+    table: the header and the range's payload bytes are read, nothing else (hz_decode_range_file)."""
+    lib = load()
+    sk = np.ascontiguousarray(seek, dtype=np.uint64)
+    out = np.empty(max(length, 1), dtype=np.uint8)
+    check(lib.hz_decode_range_file(os.fsencode(path), sk.ctypes.data_as(ctypes.c_void_p), offset, length,
+                                   out.ctypes.data_as(ctypes.c_void_p)), "hz_decode_range_file")
+    return out[:length].tobytes()
+
+
 def decode_ranges(blob, seek, ranges):
     """[(offset, length), ...] byte ranges of the original from a .compressed image and its seek table,
     decoded in one device call (hz_decode_ranges_host): a list of bytes, in the ranges' order."""
@@ -328,6 +368,25 @@ class Device:
 
     def indexless_decode(self, nsym, d_out, d_end_bit=None):
         check(self.lib.hz_indexless_decode(self.h, nsym, d_out, d_end_bit), "hz_indexless_decode")
+
+    # -- the seek table from the index-less walk (no block index) ------------------------------------
+    def seek_build(self, d_payload, payload_bytes, start_bit, nsym, d_seek):
+        """The seek table of a bare payload into d_seek (seek_bytes(nsym) bytes): nothing decoded."""
+        check(self.lib.hz_seek_build(self.h, d_payload, payload_bytes, start_bit, nsym, d_seek), "hz_seek_build")
+
+    def decode_indexless_seek(self, d_payload, payload_bytes, start_bit, nsym, d_out, d_seek, d_end_bit=None,
+                              sym_base=0, bit_base=0, stream_nsym=None):
+        """decode_indexless that also writes the call's seek entries into the stream's table d_seek. The
+        call covers codewords [sym_base, sym_base + nsym) of a stream of stream_nsym (default: nsym);
+        entries are bits from byte 0 of d_payload plus bit_base. d_out None: table only."""
+        check(self.lib.hz_decode_indexless_seek(self.h, d_payload, payload_bytes, start_bit, nsym, d_out, d_end_bit,
+                                                sym_base, bit_base, nsym if stream_nsym is None else stream_nsym,
+                                                d_seek), "hz_decode_indexless_seek")
+
+    def indexless_seek(self, sym_base, nsym, stream_nsym, d_seek):
+        """The seek entries of the pending part (after indexless_scan / _refix): its first codeword is
+        codeword sym_base of the stream, nsym its codewords; values are the scan's stream bits."""
+        check(self.lib.hz_indexless_seek(self.h, sym_base, nsym, stream_nsym, d_seek), "hz_indexless_seek")
 
     def generate(self, d_out, n, offset=0, kind=1, alpha=1.1, seed=42):
         check(self.lib.hz_generate(self.h, d_out, n, offset, kind, alpha, seed), "hz_generate")

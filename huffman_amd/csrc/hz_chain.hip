@@ -746,6 +746,154 @@ __global__ __launch_bounds__(kSyncThreads) void k_chain_tail(DecArgs a, ChainArg
     }
 }
 
+// ---- the seek table as a by-product of the walk (DESIGN.md "Seek table from the walk") ----------------
+// Entries b0 .. b0 + nent - 1 of a stream's seek table from a call that covers codewords
+// [sym_base, sym_base + nsym) of the stream: entry b is the start of codeword min(2048 b, stream_nsym)
+// - sym_base of the call. Positions are view bits until they are stored.
+struct ChainSeekArgs {
+    unsigned long long* seek;  // the table, addressed from entry 0
+    unsigned long long* end;   // nullable: the start of codeword nsym (= the end of nsym - 1), view bit + base
+    uint64_t b0, nent;
+    uint64_t sym_base, nsym, stream_nsym;
+    uint64_t base;             // stream bit of view bit 0
+    uint64_t add;              // what an entry adds to its view bit: base + the caller's bit_base
+    uint64_t limit;            // bits the view holds: a codeword of the call is held when it starts below them,
+                               // the call's end (codeword nsym, the next call's first) when it starts at or below
+    unsigned long long* stats; // nullable (k_chain_seek): entries found [0] in a head, [1] past the record
+                               // capacity, [2] through the delta rebuild, [3] in a chain that has a head
+                               // (hz_debug_seek_stats: what the tests pin)
+};
+
+// Codeword of the call that lane i of a seek pass locates: an entry's, or (i == nent) the end's.
+HZ_DEV uint64_t seek_sym(const ChainSeekArgs& z, uint64_t i) {
+    if (i == z.nent) return z.nsym;
+    const uint64_t s = (z.b0 + i) * (uint64_t)kBlockSyms;
+    return (s < z.stream_nsym ? s : z.stream_nsym) - z.sym_base;
+}
+
+HZ_DEV void seek_put(const ChainSeekArgs& z, uint64_t i, uint64_t p) {
+    // a codeword that starts exactly at the view's end has no bit in it: only the call's end may stand there
+    const bool held = p != ~0ull && (seek_sym(z, i) == z.nsym ? p <= z.limit : p < z.limit);
+    if (i == z.nent) *z.end = held ? p + z.base : ~0ull;
+    else z.seek[z.b0 + i] = held ? p + z.add : ~0ull;
+}
+
+// Stream bit of record m (< cap, walked) of chain c. chain_rec_pos is exact while the record lies
+// within 65 536 bits of its checkpoint; a decode block of 2048 codewords of up to 56 bits spans up to
+// 114 688, and then the position is rebuilt from the deltas of consecutive records (at most 8 x 56
+// bits apart), as the block decoder does (dec_chain_offsets); wide: that path was taken.
+HZ_DEV uint64_t chain_rec_pos_wide(const ChainArgs& y, uint64_t c, uint32_t m, bool& wide) {
+    const unsigned long long* ckp = y.ckpt + c * (y.bpc + 1);
+    const uint16_t* rc = y.rec + c * y.cap;
+    const uint32_t j = m / kChainRecs;
+    uint64_t p = ckp[j];
+    wide = ckp[j + 1] - p >= 65536ull;
+    if (!wide) return p + (uint16_t)(rc[m] - (uint16_t)p);
+    uint16_t prev = (uint16_t)p;
+    for (uint32_t i = j * kChainRecs + 1; i <= m; ++i) {
+        const uint16_t v = rc[i];
+        p += (uint16_t)(v - prev);
+        prev = v;
+    }
+    return p;
+}
+
+// Start of the codeword k codewords after the one at view bit p (all ones: an invalid code on the way).
+HZ_DEV uint64_t seek_walk(const DecArgs& a, const uint32_t* lds, uint64_t p, uint64_t k) {
+    if (k == 0) return p;
+    BitReader r;
+    br_init(r, a, p + a.bit_adj);
+    for (uint64_t t = 0; t < k; ++t) {
+        uint32_t sym;
+        const uint32_t L = br_next<DEC_LUT>(r, a, lds, sym);
+        if (L == 0) { atomicOr(a.err, 2u); return ~0ull; }
+        p += L;
+    }
+    return p;
+}
+
+// One lane per entry (and one for the end bit): a binary search over the chains' output indices, then
+// k_chain_tail's end-bit computation for that codeword -- the record at or before it and at most 7
+// codewords, or a serial walk through a head or past the record capacity. One lane per entry and not
+// one per chain: a chain holds anything from no entry to dozens (it is cbits bits long, an entry is
+// 2048 codewords, and a run of short codes packs many entries into one chain), so lanes per chain would
+// loop over uneven counts, while the search costs every entry the same ~log2(nchains) cached loads.
+__global__ __launch_bounds__(kSyncThreads) void k_chain_seek(DecArgs a, ChainArgs y, ChainSeekArgs z) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    copy_lds_table(lds, a.lds_img, a.lds_words);
+    const uint64_t total = y.info[3];  // codewords of the part (k_chain_meta)
+    const uint64_t n = z.nent + (z.end ? 1 : 0);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t S = seek_sym(z, i);
+        uint64_t p = ~0ull;  // past the part's codewords: not held
+        if (S == total) {
+            p = y.info[4];  // the first codeword after the part: the last chain's true exit
+        } else if (S < total) {
+            // the last chain with first <= S: chains without codewords repeat their successor's first,
+            // so the search never ends on one (first[0] = 0 <= S)
+            uint64_t lo = 0, hi = y.nchains;
+            while (hi - lo > 1) {
+                const uint64_t mid = lo + (hi - lo) / 2;
+                if (y.first[mid] <= S) lo = mid;
+                else hi = mid;
+            }
+            const uint64_t c = lo, k = S - y.first[c];
+            const uint32_t h = y.hd[c], r0 = y.r0[c];
+            int path = -1;  // the rare paths, counted
+            if (k < h) {  // in the head: from the chain's true entry
+                p = seek_walk(a, lds, c ? y.txit[c - 1] : y.entry0, k);
+                path = 0;
+            } else {
+                const uint64_t q = k - h, m = r0 + q / 8;
+                if (m < y.cap) {
+                    bool wide;
+                    p = seek_walk(a, lds, chain_rec_pos_wide(y, c, (uint32_t)m, wide), q % 8);
+                    path = wide ? 2 : -1;
+                } else {  // past the capacity
+                    p = seek_walk(a, lds, y.ckpt[c * (y.bpc + 1) + y.bpc], 8 * (m - y.cap) + q % 8);
+                    path = 1;
+                }
+            }
+            if (path >= 0 && z.stats) atomicAdd(z.stats + path, 1ull);
+            if (h && z.stats) atomicAdd(z.stats + 3, 1ull);
+        }
+        seek_put(z, i, p);
+    }
+}
+
+// Payloads under 16 bytes (k_decode_tiny's case): one thread walks from the start and stores the
+// entries (at most two lie within 128 codewords) and the end as it passes them.
+__global__ __launch_bounds__(64) void k_seek_tiny(DecArgs a, uint64_t start, ChainSeekArgs z) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    copy_lds_table(lds, a.lds_img, a.lds_words);
+    if (threadIdx.x) return;
+    BitReader r;
+    br_init(r, a, start + a.bit_adj);
+    uint64_t p = start, at = 0;
+    bool bad = false;
+    const uint64_t n = z.nent + (z.end ? 1 : 0);
+    for (uint64_t i = 0; i < n; ++i) {  // ascending codewords
+        const uint64_t S = seek_sym(z, i);
+        while (!bad && at < S && p <= z.limit) {  // (every code >= 1 bit: at most 129 steps in all)
+            uint32_t sym;
+            const uint32_t L = br_next<DEC_LUT>(r, a, lds, sym);
+            if (L == 0) { atomicOr(a.err, 2u); bad = true; break; }
+            p += L;
+            ++at;
+        }
+        seek_put(z, i, !bad && at == S ? p : ~0ull);
+    }
+}
+
+// FIXED16: codeword S of the call starts at view bit start + 16 S; the call holds `total` codewords.
+__global__ __launch_bounds__(256) void k_seek_fixed16(uint64_t start, uint64_t total, ChainSeekArgs z) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= z.nent) return;
+    const uint64_t S = seek_sym(z, i);
+    seek_put(z, i, S <= total ? start + 16 * S : ~0ull);
+}
+
 // ---- host side -----------------------------------------------------------------------------
 // Chain geometry of a part of the payload (bits [pbeg, pend) after start): chains of cbits bits, about
 // one per walk lane of the device (16 waves per CU), but at least kChainMinBlocks decode block long;
@@ -759,7 +907,7 @@ constexpr uint64_t kChainMinBlocks = 1;
 struct ChainGeom {
     uint64_t nchains = 0, cbits = 0, pbeg = 0, pend = 0;
     uint32_t bpc = 0, cap = 0;
-    uint64_t off_rec, off_ckpt, off_arr, off_u32, off_list, off_info, off_tiles, off_blk, words;
+    uint64_t off_rec, off_ckpt, off_arr, off_u32, off_list, off_info, off_tiles, off_blk, off_seek, words;
 };
 
 static ChainGeom chain_geom(uint64_t pbeg, uint64_t pend, double avg, int ncu) {
@@ -773,6 +921,10 @@ static ChainGeom chain_geom(uint64_t pbeg, uint64_t pend, double avg, int ncu) {
     const uint64_t minbits = (uint64_t)(kChainMinBlocks * kBlockSyms * avg);
     uint64_t cb = (bits + lanes - 1) / lanes;
     cb = cb > minbits ? cb : minbits;
+    // test hook: HZ_CHAIN_MIN_BITS=<bits> (read once) makes chains at least that long, so a small stream
+    // has chains whose decode blocks span 65 536 bits and more (chain_rec_pos_wide's delta rebuild)
+    static const uint64_t floor_bits = [] { const char* v = getenv("HZ_CHAIN_MIN_BITS"); return v ? strtoull(v, nullptr, 10) : 0ull; }();
+    cb = cb > floor_bits ? cb : floor_bits;
     cb = (cb + 127) & ~127ull;
     g.cbits = cb;
     g.nchains = (bits + cb - 1) / cb;
@@ -790,6 +942,7 @@ static ChainGeom chain_geom(uint64_t pbeg, uint64_t pend, double avg, int ncu) {
     g.off_info = w;  w += 8;
     g.off_tiles = w; w += ntiles + 2;
     g.off_blk = w;   w += nc * g.bpc * (sizeof(ChainBlk) / 8);
+    g.off_seek = w;  w += 4;                                    // k_chain_seek's path counters
     g.words = w + 8;
     return g;
 }
@@ -879,11 +1032,15 @@ struct ChainState {
     WalkArgs w;
     unsigned long long* tiles = nullptr;  // scan scratch
     uint64_t base = 0;                     // stream bit of byte 0 of the payload view (hz_indexless_scan)
+    uint64_t view_bits = 0;                // bits the payload view holds (chain_seek: what lies past them is not held)
+    unsigned long long* seek_stats = nullptr;  // the last chain_seek's path counters (in the scratch)
     bool valid = false;
 };
 ChainState* chain_state_create() { return new ChainState(); }
 void chain_state_destroy(ChainState* st) { delete st; }
 const unsigned long long* chain_info(const ChainState* st) { return st->valid ? st->y.info : nullptr; }
+const unsigned long long* chain_seek_stats(const ChainState* st) { return st->seek_stats; }
+void chain_forget_seek_stats(ChainState* st) { st->seek_stats = nullptr; }
 void chain_invalidate(ChainState* st) { st->valid = false; }
 
 // The part's summary in stream bits: codewords, true exit, entry in use (view bits + base).
@@ -942,6 +1099,7 @@ hipError_t chain_scan(ChainState* st, const Tables& t, const uint8_t* d_payload,
     // bits of the view from here on: stream bit b is view bit b - base (mod 2^64: start_bit may lie
     // before the view when it begins inside the stream)
     st->base = base;
+    st->view_bits = payload_bytes * 8;
     start_bit -= base;
     if (entry0 != ~0ull) entry0 -= base;
     if (!seg_decode_supported(t)) return hipErrorInvalidValue;
@@ -972,6 +1130,7 @@ hipError_t chain_scan(ChainState* st, const Tables& t, const uint8_t* d_payload,
     y.blk = reinterpret_cast<ChainBlk*>(sc + g.off_blk);
     y.err = d_err;
     st->tiles = sc + g.off_tiles;
+    st->seek_stats = nullptr;
     WalkArgs& w = st->w;
     w.words = d.words; w.nwords = d.nwords; w.bit_adj = d.bit_adj;
     w.start = start_bit; w.nseg = 0;
@@ -1061,6 +1220,78 @@ hipError_t chain_decode(ChainState* st, const Tables& t, uint64_t nsym, uint8_t*
         }
     }
     cap_check(s, "tail+end");
+    return hipGetLastError();
+}
+
+// The entries a call over codewords [sym_base, sym_base + nsym) of a stream of stream_nsym writes:
+// every b with sym_base <= min(2048 b, stream_nsym) <= sym_base + nsym.
+static void seek_entries(ChainSeekArgs& z, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym) {
+    z.sym_base = sym_base;
+    z.nsym = nsym;
+    z.stream_nsym = stream_nsym;
+    z.b0 = (sym_base + kBlockSyms - 1) / kBlockSyms;
+    const uint64_t e = sym_base + nsym;
+    const uint64_t b1 = e == stream_nsym ? index_blocks(stream_nsym) : e / kBlockSyms;  // the last entry
+    z.nent = b1 >= z.b0 ? b1 - z.b0 + 1 : 0;
+}
+
+hipError_t chain_seek(ChainState* st, const Tables& t, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym,
+                      uint64_t bit_base, unsigned long long* d_seek, unsigned long long* d_end, int ncu, hipStream_t s) {
+    if (!st->valid) return hipErrorInvalidValue;
+    ChainSeekArgs z;
+    seek_entries(z, sym_base, nsym, stream_nsym);
+    z.seek = d_seek;
+    z.end = d_end;
+    z.base = st->base;
+    z.add = st->base + bit_base;
+    z.limit = st->view_bits;
+    z.stats = reinterpret_cast<unsigned long long*>(st->y.rec) - st->g.off_rec + st->g.off_seek;  // (the scratch)
+    const uint64_t n = z.nent + (d_end ? 1 : 0);
+    if (n == 0) return hipSuccess;
+    hipError_t e;
+    if ((e = hipMemsetAsync(z.stats, 0, 32, s)) != hipSuccess) return e;
+    st->seek_stats = z.stats;
+    if ((e = ensure_lds_limit((const void*)k_chain_seek, kLdsBytes)) != hipSuccess) return e;
+    const uint64_t wgs = grid_clamp((n + kSyncThreads - 1) / kSyncThreads, (uint64_t)ncu);
+    hipLaunchKernelGGL(k_chain_seek, dim3(wgs), dim3(kSyncThreads), t.chain_lds_bytes, s, st->d, st->y, z);
+    cap_check(s, "seek");
+    return hipGetLastError();
+}
+
+hipError_t chain_seek_tiny(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                           uint64_t nsym, uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym,
+                           unsigned long long* d_seek, unsigned long long* d_end, uint32_t* d_err, hipStream_t s) {
+    if (!seg_decode_supported(t)) return hipErrorInvalidValue;
+    DecArgs d;
+    fill_chain_dec_args(d, t, d_payload, payload_bytes, nsym);
+    d.starts = nullptr; d.subs = nullptr; d.out = nullptr; d.err = d_err;
+    ChainSeekArgs z;
+    seek_entries(z, sym_base, nsym, stream_nsym);
+    z.seek = d_seek;
+    z.end = d_end;
+    z.base = 0;
+    z.add = bit_base;
+    z.limit = payload_bytes * 8;
+    z.stats = nullptr;
+    if (z.nent + (d_end ? 1 : 0) == 0) return hipSuccess;
+    hipError_t e = ensure_lds_limit((const void*)k_seek_tiny, kLdsBytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_seek_tiny, dim3(1), dim3(64), t.chain_lds_bytes, s, d, start_bit, z);
+    return hipGetLastError();
+}
+
+hipError_t seek_fixed16(uint64_t start_bit, uint64_t total, uint64_t limit, uint64_t sym_base, uint64_t nsym,
+                        uint64_t stream_nsym, uint64_t bit_base, unsigned long long* d_seek, hipStream_t s) {
+    ChainSeekArgs z;
+    seek_entries(z, sym_base, nsym, stream_nsym);
+    z.seek = d_seek;
+    z.end = nullptr;
+    z.base = 0;
+    z.add = bit_base;
+    z.limit = limit;
+    z.stats = nullptr;
+    if (z.nent == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seek_fixed16, dim3((z.nent + 255) / 256), dim3(256), 0, s, start_bit, total, z);
     return hipGetLastError();
 }
 

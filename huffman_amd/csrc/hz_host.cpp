@@ -389,6 +389,7 @@ static int ensure_scratch(hz_ctx* c, uint64_t words) {
     if (c->desc_cap >= words) return HZ_OK;
     HZ_TRY(hipStreamSynchronize(c->stream));
     (void)hipFree(c->d_desc);
+    chain_forget_seek_stats(c->chain);
     c->d_desc = nullptr;
     c->desc_cap = 0;
     HZ_TRY(hipMalloc(&c->d_desc, words * sizeof(unsigned long long)));
@@ -541,23 +542,32 @@ extern "C" int hz_index_expand(hz_ctx* c, const uint8_t* d_payload, uint64_t pay
     });
 }
 
-extern "C" int hz_decode_indexless(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
-                                   uint64_t nsym, uint8_t* d_out, uint64_t* d_end_bit) {
-    if (!c) return HZ_EINVAL;
-    if (nsym == 0) return HZ_OK;
-    if (!d_payload || !d_out || (((uintptr_t)d_out) & 15)) return HZ_EINVAL;
-    if (c->t.dec_mode < 0) return HZ_EINVAL;
+// Where a call's codewords lie in a longer stream and the table that takes their seek entries
+// (hz_decode_indexless_seek); null: no table (hz_decode_indexless).
+struct SeekReq {
+    uint64_t sym_base, bit_base, stream_nsym;
+    unsigned long long* d_seek;
+};
+
+// hz_decode_indexless, and with sk its seek entries too; d_out null (with sk only): nothing decoded, the
+// end bit from the seek pass.
+static int decode_indexless_impl(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                                 uint64_t nsym, uint8_t* d_out, uint64_t* d_end_bit, const SeekReq* sk) {
     HZ_TRY(hipSetDevice(c->device));
     payload_bytes = clamp_reach(c, payload_bytes, start_bit, nsym);
+    unsigned long long* d_end = reinterpret_cast<unsigned long long*>(d_end_bit);
     if (c->t.dec_mode == DEC_FIXED16) {
         // every code 16 bits: symbol i at start_bit + 16 i, so no index and no walk (stream-ordered)
         const uint64_t endb = nsym <= (UINT64_MAX - start_bit) / 16 ? start_bit + 16 * nsym : ~0ull;
         const bool fits = endb <= payload_bytes * 8;  // else: the end bit past the payload, nothing decoded
         return timed_stage(c, HZ_STAGE_EXTRACT, "put_u64 / launch_decode (FIXED16)", [&] {
             hipError_t e = d_end_bit ? put_u64(d_end_bit, fits ? endb : ~0ull, c->stream) : hipSuccess;
-            if (e == hipSuccess && fits)
+            if (e == hipSuccess && fits && d_out)
                 e = launch_decode(c->t, d_payload, payload_bytes, nsym, nullptr, d_out, c->d_err, c->ncu, c->stream,
                                   start_bit);
+            if (e == hipSuccess && sk)
+                e = seek_fixed16(start_bit, nsym, payload_bytes * 8, sk->sym_base, nsym, sk->stream_nsym, sk->bit_base,
+                                 sk->d_seek, c->stream);
             return e;
         });
     }
@@ -566,8 +576,13 @@ extern "C" int hz_decode_indexless(hz_ctx* c, const uint8_t* d_payload, uint64_t
     if (rc) return rc;
     if (payload_bytes < 16)  // too short for the walk: one thread, serially (stream-ordered too)
         return timed_stage(c, HZ_STAGE_EXTRACT, "chain_decode_tiny", [&] {
-            return chain_decode_tiny(c->t, d_payload, payload_bytes, start_bit, nsym, d_out,
-                                     reinterpret_cast<unsigned long long*>(d_end_bit), c->d_err, c->stream);
+            hipError_t e = hipSuccess;
+            if (d_out)
+                e = chain_decode_tiny(c->t, d_payload, payload_bytes, start_bit, nsym, d_out, d_end, c->d_err, c->stream);
+            if (e == hipSuccess && sk)
+                e = chain_seek_tiny(c->t, d_payload, payload_bytes, start_bit, nsym, sk->sym_base, sk->bit_base,
+                                    sk->stream_nsym, sk->d_seek, d_out ? nullptr : d_end, c->d_err, c->stream);
+            return e;
         });
     // stream-ordered from here: walk, fix-ups, scans, block decode, tails (no host synchronisation
     // unless the context's scratch has to grow)
@@ -576,12 +591,39 @@ extern "C" int hz_decode_indexless(hz_ctx* c, const uint8_t* d_payload, uint64_t
     return timed_stage(c, HZ_STAGE_EXTRACT, "chain_scan / chain_decode", [&] {
         hipError_t e = chain_scan(c->chain, c->t, d_payload, payload_bytes, 0, start_bit, nsym, 0, pbits, ~0ull,
                                   c->d_desc, c->d_err, c->ncu, c->stream);
-        if (e == hipSuccess)
-            e = chain_decode(c->chain, c->t, nsym, d_out, reinterpret_cast<unsigned long long*>(d_end_bit), c->ncu,
-                             c->stream);
+        if (e == hipSuccess && d_out) e = chain_decode(c->chain, c->t, nsym, d_out, d_end, c->ncu, c->stream);
+        if (e == hipSuccess && sk)  // table only: the seek pass finds the end bit, no decode and no tail
+            e = chain_seek(c->chain, c->t, sk->sym_base, nsym, sk->stream_nsym, sk->bit_base, sk->d_seek,
+                           d_out ? nullptr : d_end, c->ncu, c->stream);
         if (e == hipSuccess) chain_invalidate(c->chain);  // not a part: hz_indexless_refix / _decode may not continue it
         return e;
     });
+}
+
+extern "C" int hz_decode_indexless(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                                   uint64_t nsym, uint8_t* d_out, uint64_t* d_end_bit) {
+    if (!c) return HZ_EINVAL;
+    if (nsym == 0) return HZ_OK;
+    if (!d_payload || !d_out || (((uintptr_t)d_out) & 15)) return HZ_EINVAL;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    return decode_indexless_impl(c, d_payload, payload_bytes, start_bit, nsym, d_out, d_end_bit, nullptr);
+}
+
+extern "C" int hz_decode_indexless_seek(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                                        uint64_t nsym, uint8_t* d_out, uint64_t* d_end_bit, uint64_t sym_base,
+                                        uint64_t bit_base, uint64_t stream_nsym, uint64_t* d_seek) {
+    if (!c || !d_seek || (((uintptr_t)d_out) & 15)) return HZ_EINVAL;
+    if (sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    if (nsym == 0) return HZ_OK;
+    if (!d_payload) return HZ_EINVAL;
+    const SeekReq sk{sym_base, bit_base, stream_nsym, reinterpret_cast<unsigned long long*>(d_seek)};
+    return decode_indexless_impl(c, d_payload, payload_bytes, start_bit, nsym, d_out, d_end_bit, &sk);
+}
+
+extern "C" int hz_seek_build(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                             uint64_t nsym, uint64_t* d_seek) {
+    return hz_decode_indexless_seek(c, d_payload, payload_bytes, start_bit, nsym, nullptr, nullptr, 0, 0, nsym, d_seek);
 }
 
 // ---- one stream over several devices: the index-less decode in parts -----------------
@@ -670,6 +712,33 @@ extern "C" int hz_indexless_decode(hz_ctx* c, uint64_t nsym, uint8_t* d_out, uin
     HZ_TRY(chain_decode(c->chain, c->t, nsym, d_out, reinterpret_cast<unsigned long long*>(d_end_bit), c->ncu,
                         c->stream));
     return arm_err_check(c);
+}
+
+extern "C" int hz_indexless_seek(hz_ctx* c, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym, uint64_t* d_seek) {
+    if (!c || !d_seek) return HZ_EINVAL;
+    if (sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
+    unsigned long long* sk = reinterpret_cast<unsigned long long*>(d_seek);
+    if (c->fx.on) {  // stream bits throughout: the part's codeword S at entry + 16 S
+        HZ_TRY(hipSetDevice(c->device));
+        HZ_TRY(seek_fixed16(c->fx.entry, (c->fx.xit - c->fx.entry) / 16, c->fx.base + 8 * c->fx.bytes, sym_base, nsym,
+                            stream_nsym, 0, sk, c->stream));
+        return arm_err_check(c);
+    }
+    if (!chain_info(c->chain)) return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    HZ_TRY(chain_seek(c->chain, c->t, sym_base, nsym, stream_nsym, 0, sk, nullptr, c->ncu, c->stream));
+    return arm_err_check(c);
+}
+
+// Debug (not in the public header; tests/test_gpu_seek_build.py pins the rare paths with it): how many
+// entries the context's last k_chain_seek found in a head, past the record capacity, through the
+// delta rebuild and in a chain that has a head (4 x u64). Synchronises the stream. HZ_EINVAL: no such pass since the scratch last grew.
+extern "C" int hz_debug_seek_stats(hz_ctx* c, uint64_t* out) {
+    if (!c || !out || !chain_seek_stats(c->chain)) return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    HZ_TRY(hipStreamSynchronize(c->stream));
+    HZ_TRY(hipMemcpy(out, chain_seek_stats(c->chain), 32, hipMemcpyDeviceToHost));
+    return HZ_OK;
 }
 
 // Zipf thresholds: thr[r-1] = floor(2^64 * sum_{j<=r} j^-alpha / H); thr[255] = max.

@@ -1,8 +1,11 @@
 // hz_image.cpp -- the whole-buffer flows behind hz_*_host (used by the tests and the Python package): a
 // complete .compressed image in host memory encoded, decoded, indexed and decoded by ranges on the
 // process-wide context, device work inside.
+#include <fcntl.h>
 #include <stdint.h>
 #include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <memory>
@@ -77,9 +80,16 @@ int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint3
     return HZ_OK;
 }
 
-// A complete .compressed image in host memory, opened: the header parsed, the payload located.
+// A complete .compressed image, opened: the header parsed, the payload located. In host memory (open), or
+// a file on disk (open_file) of which only the header and the payload bytes asked for are read.
 struct OpenedImage {
     const uint8_t* f = nullptr;
+    int fd = -1;                    // open_file: the file
+    std::vector<uint8_t> head;      // open_file: its first bytes (the header is at most 12 + 65536 * 11 bytes)
+    // open_file: the payload bytes of the last upload. The async copy reads them until the caller's next
+    // hz_ctx_sync, so an image takes ONE upload per flow (every flow here does) and outlives that sync;
+    // mutable because upload() is const for the in-memory form, which needs no buffer
+    mutable std::vector<uint8_t> span;
     std::unique_ptr<hz_codebook> cb{new hz_codebook()};
     hz_header_info info;
     uint64_t nsym = 0;  // symbols
@@ -93,6 +103,30 @@ struct OpenedImage {
         pay = len - info.payload_byte;
         return HZ_OK;
     }
+    ~OpenedImage() { if (fd >= 0) ::close(fd); }
+    int open_file(const char* path) {
+        struct stat st;
+        if (stat(path, &st) != 0) return HZ_ENOENT;
+        fd = ::open(path, O_RDONLY);
+        if (fd < 0) return HZ_EIO;
+        const uint64_t fsize = (uint64_t)st.st_size;
+        head.resize(std::min<uint64_t>(fsize, 1u << 20));
+        int rc = read_at(head.data(), head.size(), 0);
+        if (rc) return rc;
+        if ((rc = hz_header_parse(head.data(), head.size(), cb.get(), &info))) return rc;
+        if (info.payload_byte > fsize) return HZ_EFORMAT;
+        nsym = info.n / 2;
+        pay = fsize - info.payload_byte;
+        return HZ_OK;
+    }
+    int read_at(uint8_t* dst, uint64_t n, uint64_t off) const {
+        for (uint64_t done = 0; done < n;) {
+            const ssize_t r = ::pread(fd, dst + done, n - done, (off_t)(off + done));
+            if (r <= 0) return HZ_EIO;
+            done += (uint64_t)r;
+        }
+        return HZ_OK;
+    }
     // every codeword is >= min_len bits: a header claiming more symbols than the
     // payload can hold is malformed (checked before anything is allocated)
     bool holds_its_symbols() const {
@@ -104,7 +138,14 @@ struct OpenedImage {
         const int rc = d.alloc(e - b + 16);
         if (rc) return rc;
         HZ_TRY(hipMemsetAsync(d.p, 0, e - b + 16, c->stream));
-        HZ_TRY(hipMemcpyAsync(d.p, f + info.payload_byte + b, e - b, hipMemcpyHostToDevice, c->stream));
+        const uint8_t* src = f ? f + info.payload_byte + b : nullptr;
+        if (!f) {  // from the file: these bytes and no others
+            span.resize(e - b);
+            const int r2 = read_at(span.data(), e - b, info.payload_byte + b);
+            if (r2) return r2;
+            src = span.data();
+        }
+        HZ_TRY(hipMemcpyAsync(d.p, src, e - b, hipMemcpyHostToDevice, c->stream));
         return HZ_OK;
     }
 };
@@ -155,7 +196,7 @@ int decode_image(const uint8_t* f, uint64_t len, std::vector<uint8_t>& out) {
     return HZ_OK;
 }
 
-// The seek table of a complete .compressed image: hz_index_build's start[].
+// The seek table of a complete .compressed image: hz_seek_build's (the index-less walk's; no block index).
 int seek_build_image(const uint8_t* f, uint64_t len, uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym_out) {
     OpenedImage im;
     int rc = im.open(f, len);
@@ -170,20 +211,17 @@ int seek_build_image(const uint8_t* f, uint64_t len, uint64_t* seek, uint64_t ca
     if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
     DevBuf dpay, didx;
     if ((rc = im.upload(c, 0, im.pay, dpay))) return rc;
-    if ((rc = didx.alloc(hz_index_bytes(im.nsym)))) return rc;
-    if ((rc = hz_index_build(c, (const uint8_t*)dpay.p, im.pay, im.info.payload_bit, im.nsym, (uint64_t*)didx.p))) return rc;
+    if ((rc = didx.alloc(hz_seek_bytes(im.nsym)))) return rc;
+    if ((rc = hz_seek_build(c, (const uint8_t*)dpay.p, im.pay, im.info.payload_bit, im.nsym, (uint64_t*)didx.p))) return rc;
     HZ_TRY(hipMemcpyAsync(seek, didx.p, hz_seek_bytes(im.nsym), hipMemcpyDeviceToHost, c->stream));
     if ((rc = hz_ctx_sync(c))) return rc;
     if (seek[index_blocks(im.nsym)] > im.pay * 8) return HZ_EFORMAT;  // fewer than nsym codewords in the payload
     return HZ_OK;
 }
 
-// Bytes [offset, offset + count) of the original of a complete .compressed image, from its seek table.
-int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uint64_t offset, uint64_t count,
-                       uint8_t* out) {
-    OpenedImage im;
-    int rc = im.open(f, len);
-    if (rc) return rc;
+// Bytes [offset, offset + count) of the original of an opened image, from its seek table.
+int decode_range_opened(const OpenedImage& im, const uint64_t* seek, uint64_t offset, uint64_t count, uint8_t* out) {
+    int rc;
     if (offset > im.info.n || count > im.info.n - offset) return HZ_EINVAL;
     if (count == 0) return HZ_OK;
     if (!out) return HZ_EINVAL;
@@ -214,6 +252,13 @@ int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uin
     }
     if (im.info.is_odd && offset + count == im.info.n) out[count - 1] = (uint8_t)im.info.last_byte;
     return HZ_OK;
+}
+
+int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uint64_t offset, uint64_t count,
+                       uint8_t* out) {
+    OpenedImage im;
+    const int rc = im.open(f, len);
+    return rc ? rc : decode_range_opened(im, seek, offset, count, out);
 }
 
 // Byte ranges [offsets[i], offsets[i] + counts[i]) of the original, concatenated in `out`: one
@@ -333,4 +378,13 @@ extern "C" int hz_decode_ranges_host(const uint8_t* file, uint64_t len, const ui
                                      const uint64_t* counts, uint32_t nranges, uint8_t* out) {
     if (!file) return HZ_EINVAL;
     return guarded([&] { return decode_ranges_image(file, len, seek, offsets, counts, nranges, out); });
+}
+
+extern "C" int hz_decode_range_file(const char* path, const uint64_t* seek, uint64_t offset, uint64_t count, uint8_t* out) {
+    if (!path) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open_file(path);
+        return rc ? rc : decode_range_opened(im, seek, offset, count, out);
+    });
 }

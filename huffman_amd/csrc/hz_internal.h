@@ -384,6 +384,24 @@ hipError_t chain_decode(ChainState* st, const Tables& t, uint64_t nsym, uint8_t*
 // payloads under 16 bytes: one thread, serially, stream-ordered (d_end: the end bit or UINT64_MAX)
 hipError_t chain_decode_tiny(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
                              uint64_t nsym, uint8_t* d_out, unsigned long long* d_end, uint32_t* d_err, hipStream_t s);
+// The seek table as a by-product (DESIGN.md "Seek table from the walk"): after chain_scan / chain_refix, the
+// entries b with sym_base <= min(2048 b, stream_nsym) <= sym_base + nsym of the table at d_seek (addressed
+// from entry 0): the start bit of codeword min(2048 b, stream_nsym) - sym_base of the part, as a stream
+// bit + bit_base; all ones for a codeword the part does not hold. d_end (nullable): the start of
+// codeword nsym, i.e. chain_decode's end bit, so a table-only call runs no decode and no tail.
+hipError_t chain_seek(ChainState* st, const Tables& t, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym,
+                      uint64_t bit_base, unsigned long long* d_seek, unsigned long long* d_end, int ncu, hipStream_t s);
+// the same for payloads under 16 bytes (one thread) and for FIXED16 (codeword S of `total` at start_bit + 16 S,
+// held while it starts at or before bit `limit`)
+hipError_t chain_seek_tiny(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                           uint64_t nsym, uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym,
+                           unsigned long long* d_seek, unsigned long long* d_end, uint32_t* d_err, hipStream_t s);
+hipError_t seek_fixed16(uint64_t start_bit, uint64_t total, uint64_t limit, uint64_t sym_base, uint64_t nsym,
+                        uint64_t stream_nsym, uint64_t bit_base, unsigned long long* d_seek, hipStream_t s);
+// the last chain_seek's path counters (device, 4 x u64: entries found in a head, past the record capacity,
+// through the delta rebuild, in a chain that has a head), null when there are none; forgotten when the scratch they live in is freed
+const unsigned long long* chain_seek_stats(const ChainState* st);
+void chain_forget_seek_stats(ChainState* st);
 const unsigned long long* chain_info(const ChainState* st);
 void chain_invalidate(ChainState* st);  // the scratch or tables it points into changed
 hipError_t chain_summary(const ChainState* st, unsigned long long* d_dst, hipStream_t s);  // 3 x u64, stream bits

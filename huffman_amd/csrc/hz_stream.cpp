@@ -596,8 +596,23 @@ static int parse_header_for_extract(const std::vector<uint8_t>& head, hz_codeboo
 // the front of the other buffer before refilling it. The host's fread of the
 // next window overlaps the decode, and its fwrite of a round's output overlaps
 // the next round's upload and index-less decode (hz_decode_indexless).
-static int hz_extract_stream_impl(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose) {
-    if (!in_path || !out_path || chunk_bytes < 4096) return HZ_EINVAL;
+//
+// With a SeekSink the rounds also leave the file's seek table (hz_extract_stream_seek): every round is
+// hz_decode_indexless_seek at sym_base = the symbols done and bit_base = 8 x the payload bytes the
+// earlier rounds consumed, into one device table copied out once at the end. A round redone after an
+// overrun rewrites its entries, and later rounds overwrite what the overrun attempt wrote past its
+// window. Without an out_path (sink only) nothing is decoded, copied out or written.
+struct SeekSink {
+    uint64_t* seek;      // host, cap_bytes
+    uint64_t cap_bytes;
+    uint64_t* nsym;      // out: the file's symbols
+};
+
+static int hz_extract_stream_impl(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
+                                  const SeekSink* sink = nullptr) {
+    if (!in_path || (!out_path && !sink) || chunk_bytes < 4096) return HZ_EINVAL;
+    if (sink && !sink->nsym) return HZ_EINVAL;
+    const bool write = out_path != nullptr;
     chunk_bytes &= ~(uint64_t)15;
     struct stat st;
     if (stat(in_path, &st) != 0) return HZ_ENOENT;
@@ -612,9 +627,13 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
     std::unique_ptr<hz_codebook> cb(new hz_codebook());
     hz_header_info info;
     if ((rc = parse_header_for_extract(head, cb.get(), &info))) return rc;
+    if (sink) {
+        *sink->nsym = info.n / 2;
+        if (hz_seek_bytes(info.n / 2) && (!sink->seek || sink->cap_bytes < hz_seek_bytes(info.n / 2))) return HZ_ECAP;
+    }
     FileWriter fout;
-    if ((rc = fout.open(out_path))) return rc;
-    {
+    if (write && (rc = fout.open(out_path))) return rc;
+    if (write) {
         // Reserve no more than the payload can decode to: a header whose N overstates it (corrupt or
         // crafted) must not allocate disk before the decode rejects it. nsym codewords need at least
         // nsym * min_len payload bits.
@@ -642,22 +661,24 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
         // mean bits per symbol of this file, 3% margin (a mispredicted round is redone exactly)
         const double mean = pay_total ? ((double)pay_total * 8 - info.payload_bit) / (double)nsym : (double)max_len;
         const uint64_t sym_cap = std::max<uint64_t>(W / 2, kBlockSyms);  // output per round <= W bytes
-        DevBuf dwin[2], didx, dout;
+        DevBuf dwin[2], didx, dout, dseek;
         PinnedBuf hin, hout[2];  // hout: a round's output leaves (parallel writes) beside the next round
         int ob = 0;
         const auto ta = Clock::now();
         for (int i = 0; i < 2; ++i)
             if ((rc = dwin[i].alloc(W + 16))) return rc;
         if ((rc = didx.alloc(16))) return rc;  // the round's end bit
-        if ((rc = dout.alloc(2 * sym_cap + 16))) return rc;
+        if (write && (rc = dout.alloc(2 * sym_cap + 16))) return rc;
+        if (sink && (rc = dseek.alloc(hz_seek_bytes(nsym)))) return rc;
         if ((rc = hin.alloc(W))) return rc;
         for (int i = 0; i < 2; ++i)
-            if ((rc = hout[i].alloc(2 * sym_cap))) return rc;
+            if (write && (rc = hout[i].alloc(2 * sym_cap))) return rc;
         WriterDrain wdrain{fout};
         g_timing.alloc_ms += ms_since(ta);
         DrainGuard drain(c->stream);
         if (fseek(fp, (long)info.payload_byte, SEEK_SET) != 0) return HZ_EIO;
         uint64_t file_left = pay_total, have = 0, done = 0;
+        uint64_t consumed = 0;  // payload bytes before the window (the seek entries' bit base)
         uint64_t bit = info.payload_bit;
         int cur = 0;
         // symbols this round decodes from the window: what it surely holds
@@ -674,8 +695,10 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
         // a round: the window's first kk codewords decoded index-less into dout, and their end bit
         auto launch_index = [&](uint64_t kk) -> int {
             hipEvent_t t0 = spans.mark(c->stream);
-            int r2 = hz_decode_indexless(c, (const uint8_t*)dwin[cur].p, have, bit, kk, (uint8_t*)dout.p,
-                                         (uint64_t*)didx.p);
+            int r2 = sink ? hz_decode_indexless_seek(c, (const uint8_t*)dwin[cur].p, have, bit, kk, (uint8_t*)dout.p,
+                                                     (uint64_t*)didx.p, done, 8 * consumed, nsym, (uint64_t*)dseek.p)
+                          : hz_decode_indexless(c, (const uint8_t*)dwin[cur].p, have, bit, kk, (uint8_t*)dout.p,
+                                                (uint64_t*)didx.p);
             if (r2) return r2;
             spans.add(t0, spans.mark(c->stream), &g_timing.kernel_ms);
             HZ_TRY(hipMemcpyAsync(&end_bit, didx.p, 8, hipMemcpyDeviceToHost, c->stream));
@@ -701,9 +724,11 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
                 if ((rc = launch_index(k)) || (rc = hz_ctx_sync(c))) return rc;
             }
             if (end_bit > have * 8) return HZ_EFORMAT;    // truncated file
-            hipEvent_t t1 = spans.mark(c->stream);
-            HZ_TRY(hipMemcpyAsync(hout[ob].p, dout.p, 2 * k, hipMemcpyDeviceToHost, c->stream));
-            spans.add(t1, spans.mark(c->stream), &g_timing.d2h_ms);
+            if (write) {
+                hipEvent_t t1 = spans.mark(c->stream);
+                HZ_TRY(hipMemcpyAsync(hout[ob].p, dout.p, 2 * k, hipMemcpyDeviceToHost, c->stream));
+                spans.add(t1, spans.mark(c->stream), &g_timing.d2h_ms);
+            }
             // move the unconsumed tail to the other window and read the refill behind the decode
             const uint64_t used = end_bit / 8, tail = have - used;
             const int nxt = cur ^ 1;
@@ -727,6 +752,7 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
                 }
                 have = tail + r;
                 file_left -= r;
+                consumed += used;
                 bit = end_bit % 8;
                 cur = nxt;
                 done += kdone;
@@ -736,24 +762,37 @@ static int hz_extract_stream_impl(const char* in_path, const char* out_path, uin
                 done += kdone;
             }
             if ((rc = fout.wait())) return rc;  // the previous round's write: hout[ob ^ 1] free for the next
-            fout.start(hout[ob].p, 2 * kdone, out_off);
+            if (write) fout.start(hout[ob].p, 2 * kdone, out_off);
             out_off += 2 * kdone;
             ob ^= 1;
         }
         if ((rc = fout.wait())) return rc;
+        if (sink) {  // the table, once
+            hipEvent_t t3 = spans.mark(c->stream);
+            HZ_TRY(hipMemcpyAsync(sink->seek, dseek.p, hz_seek_bytes(nsym), hipMemcpyDeviceToHost, c->stream));
+            spans.add(t3, spans.mark(c->stream), &g_timing.d2h_ms);
+            if ((rc = hz_ctx_sync(c))) return rc;
+        }
         spans.fold();
     }
-    if (info.is_odd) {
+    if (write && info.is_odd) {
         const uint8_t b = (uint8_t)info.last_byte;
         if ((rc = fout.write_now(&b, 1, out_off))) return rc;
     }
-    if ((rc = fout.close())) return rc;
+    if (write && (rc = fout.close())) return rc;
     if (verbose) std::cout << "Decompression is complete" << std::endl;
     return HZ_OK;
 }
 
 extern "C" int hz_extract_stream(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose) {
     return timed_call([&] { return hz_extract_stream_impl(in_path, out_path, chunk_bytes, verbose); });
+}
+
+extern "C" int hz_extract_stream_seek(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
+                                      uint64_t* seek, uint64_t cap_bytes, uint64_t* nsym) {
+    if (!in_path || !nsym || chunk_bytes < 4096) return HZ_EINVAL;
+    const SeekSink sink{seek, cap_bytes, nsym};
+    return timed_call([&] { return hz_extract_stream_impl(in_path, out_path, chunk_bytes, verbose, &sink); });
 }
 
 // Compressor.cu:315-632, stdout lines kept (:335-336,385,612-631).

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .codec import Device, build_codebook, header_bits, index_bytes, payload_bits, write_header
+from .codec import Device, build_codebook, header_bits, index_bytes, payload_bits, seek_bytes, write_header
 
 
 class Plan:
@@ -179,6 +179,13 @@ class StreamCodec:
         """The complete block index from the seek table (seek may be index itself)."""
         self.dev.index_expand(payload.data_ptr(), payload.numel(), seek.data_ptr(), nsym, index.data_ptr())
         return index
+
+    def seek_build(self, payload, start_bit, nsym):
+        """The seek table (int64 tensor, seek_bytes(nsym) / 8 entries) of a bare payload from the
+        index-less walk: no block index, nothing decoded. Needs the decode tables (upload_decode)."""
+        seek = torch.empty(max(seek_bytes(nsym) // 8, 1), dtype=torch.int64, device=self.device)
+        self.dev.seek_build(payload.data_ptr(), payload.numel(), start_bit, nsym, seek.data_ptr())
+        return seek[:seek_bytes(nsym) // 8]
 
     def sync(self):
         self.dev.sync()

@@ -135,7 +135,8 @@ int hz_header_parse_device(hz_ctx *ctx, const uint8_t *d_file, uint64_t len, hz_
  * launched before it runs), staged in pinned memory and copied by one device
  * kernel per table set. The index-less decoder's tables (walk length and escape
  * tables, a DENSE codebook's chain LUT) are copied by the first call that reads
- * them (hz_decode_indexless, hz_indexless_scan, hz_index_build), in its stream
+ * them (hz_decode_indexless, hz_decode_indexless_seek / hz_seek_build,
+ * hz_indexless_scan, hz_index_build), in its stream
  * order, so a decode through a block index never copies them; under stream
  * capture that copy is part of the captured work. */
 int hz_codebook_upload(hz_ctx *ctx, const hz_codebook *cb);
@@ -350,6 +351,50 @@ int hz_index_expand(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_byte
 int hz_decode_indexless(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
                         uint64_t nsym, uint8_t *d_out, uint64_t *d_end_bit);
 
+/* ---- the seek table from the index-less walk -------------------------------
+ * After its walk, fix-ups and scans the index-less decoder knows where every 8th
+ * codeword of the stream starts, so a stream's seek table (above) is a light
+ * extra pass over that state: no block index is built (hz_index_build computes
+ * 256 chain starts per block that a seek table does not keep) and nothing has to
+ * be decoded. Entry b of a stream of stream_nsym symbols is the start bit of
+ * codeword s_b = min(2048 b, stream_nsym); the last entry is the stream's end.
+ *
+ * hz_seek_build: the seek table of a bare payload (hz_seek_bytes(nsym) bytes at
+ * d_seek), with the scratch of hz_decode_indexless and no output buffer:
+ * hz_decode_indexless_seek with d_out NULL, bases 0 and stream_nsym = nsym.
+ *
+ * hz_decode_indexless_seek: hz_decode_indexless (same arguments, same decoded
+ * bytes, same *d_end_bit) that also writes the call's seek entries. The call
+ * covers codewords [sym_base, sym_base + nsym) of a longer stream (a window of a
+ * file): it writes d_seek[b], addressed from entry 0 of the stream's table, for
+ * every b with sym_base <= s_b <= sym_base + nsym. The value is the bit at which
+ * codeword s_b - sym_base of the call starts, counted from byte 0 of d_payload,
+ * plus bit_base; for s_b = sym_base + nsym that is the call's end bit. Two
+ * adjacent calls both write their shared boundary, with equal values. A codeword
+ * the payload does not hold (it would start at or past payload_bytes * 8: one
+ * that starts exactly at the payload's end has no bit in it) gets UINT64_MAX, as
+ * hz_index_build leaves start[nblocks]; only the call's own end, codeword nsym,
+ * may stand exactly at the payload's end. d_out may be NULL: table
+ * only -- the walk, the fix-ups, the scans and the seek pass run, nothing is
+ * decoded, and *d_end_bit (optional) comes from the seek pass (UINT64_MAX where
+ * the payload holds fewer than nsym codewords).
+ *
+ * hz_indexless_seek: the same for a pending part (after hz_indexless_scan /
+ * _refix): the part's first codeword is codeword sym_base of the stream (the sum
+ * of the earlier parts' counts), nsym at most the part's codewords; values are
+ * the scan's stream bits. Does not end the pending part.
+ *
+ * Stream-ordered and capturable; the host waits only when the scratch grows.
+ * HZ_EINVAL at the call: a null d_seek, sym_base + nsym > stream_nsym, no decode
+ * tables, a non-null d_out that is not 16-byte aligned, no pending part. nsym 0:
+ * HZ_OK, nothing written. An invalid code reports HZ_EFORMAT at hz_ctx_sync. */
+int hz_seek_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                  uint64_t nsym, uint64_t *d_seek);
+int hz_decode_indexless_seek(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
+                             uint64_t nsym, uint8_t *d_out, uint64_t *d_end_bit,
+                             uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym, uint64_t *d_seek);
+int hz_indexless_seek(hz_ctx *ctx, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym, uint64_t *d_seek);
+
 /* ---- one index-less stream over several devices ------------
  * The same decode in PARTS: every device (rank) decodes the payload bits
  * [part_begin, part_end) (counted after start_bit) of one stream, found by
@@ -422,6 +467,21 @@ int hz_archive_stream(const char *in_path, const char *out_path, uint64_t chunk_
  * 256 MiB windows. Replaces the whole-file buffers of
  * Decompressor.cu:65-114,259-291. */
 int hz_extract_stream(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose);
+/* hz_extract_stream that also returns the file's seek table (bits from the file
+ * byte that holds the first payload bit, as hz_seek_build_host counts): every
+ * round is hz_decode_indexless_seek into one device table (0.2 % of the output),
+ * copied out once at the end. out_path NULL: no output file, nothing decoded,
+ * table only. *nsym receives the file's symbols; cap_bytes < hz_seek_bytes(*nsym):
+ * HZ_ECAP with *nsym set (nothing else done). Host memory: two windows and the
+ * table, whatever the file's size. A truncated file: HZ_EFORMAT. */
+int hz_extract_stream_seek(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose,
+                           uint64_t *seek, uint64_t cap_bytes, uint64_t *nsym);
+/* Bytes [offset, offset + count) of the original, from the file on disk and its
+ * host seek table, with hz_decode_range_host's semantics (odd offsets and counts,
+ * the odd last byte from the header, HZ_EINVAL past the original's size): reads
+ * the header (at most 1 MiB) and the hz_seek_span bytes of the range, nothing
+ * else. A missing file: HZ_ENOENT (before any device call). */
+int hz_decode_range_file(const char *path, const uint64_t *seek, uint64_t offset, uint64_t count, uint8_t *out);
 /* Stage split of the calling thread's last hz_archive_stream /
  * hz_extract_stream call (hz_archive_file / hz_extract_file included). Stage
  * times are busy times: host file reads and writes overlap the device's

@@ -11,8 +11,12 @@
      range), the two sides alternating in one loop and every result compared with the input: 50 random
      4 KiB ranges and 50 of 1 MiB from the seek table and with the full index, one 4 KiB range from the seek
      table; with stats[2], the most fix-up rounds any block of the run needed
+  g  the seek table from the index-less walk: hz_seek_build beside hz_index_build, and
+     hz_decode_indexless_seek (with an output) beside hz_decode_indexless, the sides of each pair
+     alternating in one loop, every repeat's table compared with pack's start[]; the by-product's cost is
+     the difference of the second pair against that pair's own spread
 
---only f runs figure f alone. Prints one JSON line (and writes it to --out)."""
+--only f / --only g runs that figure alone. Prints one JSON line (and writes it to --out)."""
 import argparse
 import json
 import os
@@ -78,6 +82,55 @@ def batch_figures(c, x, payload, index, seek, nsym, reps):
     return res
 
 
+def seek_figures(c, x, plan, payload, index, seek, nsym, reps):
+    """Figure g."""
+    nb = seek.numel() - 1
+    pp, pn, sb = payload.data_ptr(), payload.numel(), plan.start_bit
+    tab = torch.empty(nb + 1, dtype=torch.int64, device="cuda")
+    idx = torch.empty_like(index)
+    out = torch.empty(2 * nsym + 16, dtype=torch.uint8, device="cuda")
+    end = torch.zeros(2, dtype=torch.int64, device="cuda")
+
+    def seek_build():
+        c.dev.seek_build(pp, pn, sb, nsym, tab.data_ptr())
+
+    def index_build():
+        c.dev.index_build(pp, pn, sb, nsym, idx.data_ptr())
+
+    def indexless_seek():
+        c.dev.decode_indexless_seek(pp, pn, sb, nsym, out.data_ptr(), tab.data_ptr(), end.data_ptr())
+
+    def indexless():
+        c.dev.decode_indexless(pp, pn, sb, nsym, out.data_ptr(), end.data_ptr())
+
+    res = {}
+    for name, (fa, fb), (ka, kb) in (("g_table", (seek_build, index_build), ("seek_build_ms", "index_build_ms")),
+                                     ("g_byproduct", (indexless_seek, indexless),
+                                      ("decode_indexless_seek_ms", "decode_indexless_ms"))):
+        for fn in (fa, fb):  # warm-up (also sizes the scratch)
+            timed(c, fn)
+        ta, tb, ok, ok_b = [], [], True, True
+        for _ in range(reps):  # alternating
+            tab.fill_(-1)
+            idx[:nb + 1].fill_(-1)
+            end.fill_(-1)
+            c.sync()
+            ta.append(timed(c, fa))
+            ok = ok and bool(torch.equal(tab, seek))
+            if name == "g_byproduct":
+                ok = ok and int(end[0].item()) == int(seek[-1].item())
+                end.fill_(-1)
+                c.sync()
+            tb.append(timed(c, fb))
+            ok_b = ok_b and (bool(torch.equal(idx[:nb + 1], seek)) if name == "g_table"
+                             else int(end[0].item()) == int(seek[-1].item()))
+        res[name] = {ka: stats(ta), kb: stats(tb), "every_table_equals_pack": ok, "other_side_right": ok_b,
+                     "first_below_second_in_every_repeat": max(ta) < min(tb),
+                     "median_difference_ms": round(float(np.median(ta)) - float(np.median(tb)), 4)}
+    res["g_byproduct"]["output_equals_input"] = bool(torch.equal(out[:2 * nsym], x[:2 * nsym]))
+    return res
+
+
 def case(c, n, reps, only=""):
     x = torch.empty(n, dtype=torch.uint8, device="cuda")
     c.dev.generate(x.data_ptr(), n, offset=0, kind=1, alpha=1.1, seed=42)
@@ -91,6 +144,10 @@ def case(c, n, reps, only=""):
     if only == "f":
         del out
         res.update(batch_figures(c, x, payload, index, seek, nsym, reps))
+        return res
+    if only == "g":
+        del out
+        res.update(seek_figures(c, x, plan, payload, index, seek, nsym, reps))
         return res
 
     def dec():
@@ -144,6 +201,7 @@ def case(c, n, reps, only=""):
                                            "p95": round(float(np.percentile(ts, 95)), 4), "last_equals_input": ok}
     del out
     res.update(batch_figures(c, x, payload, index, seek, nsym, reps))
+    res.update(seek_figures(c, x, plan, payload, index, seek, nsym, reps))
     return res
 
 
@@ -151,7 +209,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes-gib", type=int, nargs="*", default=[1, 16])
-    ap.add_argument("--only", default="", choices=["", "f"])
+    ap.add_argument("--only", default="", choices=["", "f", "g"])
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     c = StreamCodec(0)
