@@ -1,7 +1,7 @@
 """MI355X-native Huffman codec (gfx950): drop-in for yechuan51/huffman's
 `archive` / `extract` path. See DESIGN.md and include/huffman_amd.h."""
 from ._lib import HZError, LIB_PATH, BIN_DIR, load  # noqa: F401
-from .codec import (Device, archive, archive_stream, build_codebook, codebook_arrays, decode, encode, extract, extract_stream, stream_timing,  # noqa: F401
+from .codec import (Device, archive, archive_seek, archive_stream, archive_stream_seek, encode_seek, build_codebook, codebook_arrays, decode, encode, extract, extract_stream, stream_timing,  # noqa: F401
                     header_bits, index_bytes, index_starts, parse_header, payload_bits, write_header,
                     build_seek, build_seek_file, decode_range, decode_range_file, decode_ranges, seek_bytes,
                     seek_entries, seek_span)
@@ -9,4 +9,4 @@ from .codec import (Device, archive, archive_stream, build_codebook, codebook_ar
 __all__ = ["Device", "HZError", "archive", "archive_stream", "extract", "extract_stream", "stream_timing", "encode", "decode", "build_codebook", "codebook_arrays",
            "header_bits", "payload_bits", "write_header", "parse_header", "index_bytes", "index_starts", "load", "LIB_PATH",
            "BIN_DIR", "build_seek", "build_seek_file", "decode_range", "decode_range_file", "decode_ranges", "seek_bytes",
-           "seek_entries", "seek_span"]
+           "seek_entries", "seek_span", "archive_seek", "archive_stream_seek", "encode_seek"]

@@ -99,6 +99,7 @@ PROTOTYPES = [
     ("hz_hist16_ranges", _I, [_P, _P, _U64, _P, _I, _P]),
     ("hz_pack_ranges", _I, [_P, _P, _U64, _U64, _U32, _P, _U64, _P, _P]),
     ("hz_last_pack_ranges", _I, [_P]),
+    ("hz_pack_seek", _I, [_P, _P, _U64, _U64, _U32, _P, _U64, _P, _U64, _U64, _U64, _P]),
     ("hz_decode", _I, [_P, _P, _U64, _U64, _P, _P]),
     ("hz_last_decode_chunks", _I, [_P]),
     ("hz_index_build", _I, [_P, _P, _U64, _U64, _U64, _P]),
@@ -120,10 +121,13 @@ PROTOTYPES = [
     ("hz_generate", _I, [_P, _P, _U64, _U64, _I, ctypes.c_double, _U64]),
     ("hz_archive_file", _I, [ctypes.c_char_p, _I]),
     ("hz_archive_stream", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I]),
+    ("hz_archive_stream_seek", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_archive_file_seek", _I, [ctypes.c_char_p, _I, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_extract_stream", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I]),
     ("hz_extract_file", _I, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, _I]),
     ("hz_stream_last_timing", _I, [ctypes.POINTER(StreamTiming)]),
     ("hz_encode_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_encode_host_seek", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64), _P, _U64]),
     ("hz_encoded_size", _I, [_P, _U64, ctypes.POINTER(_U64)]),
     ("hz_decode_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_seek_build_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),

@@ -41,6 +41,29 @@ def encode(data):
     return out[:got.value].tobytes()
 
 
+def _seek_table(nsym):
+    """A host seek table for nsym symbols: (the array to return, the buffer handed to the library)."""
+    words = seek_bytes(nsym) // 8
+    buf = np.zeros(max(words, 1), dtype=np.uint64)
+    return buf[:words], buf
+
+
+def encode_seek(data):
+    """Bytes -> (complete .compressed image, its seek table): encode() with the table the writer knows
+    while it packs (uint64 start[nblocks + 1], as build_seek counts), no pass over the finished image."""
+    lib = load()
+    arr, p = _buf(data)
+    n = arr.size
+    need = ctypes.c_uint64()
+    check(lib.hz_encoded_size(p, n, ctypes.byref(need)), "hz_encoded_size")
+    out = np.empty(max(need.value, 1), dtype=np.uint8)
+    seek, buf = _seek_table(n // 2)
+    got = ctypes.c_uint64()
+    check(lib.hz_encode_host_seek(p, n, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(got),
+                                  buf.ctypes.data_as(ctypes.c_void_p), buf.size * 8), "hz_encode_host_seek")
+    return out[:got.value].tobytes(), seek
+
+
 def decode(blob):
     """.compressed image -> original bytes (what `extract` writes)."""
     lib = load()
@@ -65,6 +88,27 @@ def archive_stream(path, out_path, chunk_bytes=1 << 30, verbose=False):
     check(load().hz_archive_stream(str(path).encode(), str(out_path).encode(), chunk_bytes, int(verbose)),
           "hz_archive_stream")
     return str(out_path)
+
+
+def archive_seek(path, verbose=True):
+    """archive() that also returns the file's seek table, from the writer: (name, seek). The table is
+    what build_seek_file(name) would find, without reading the .compressed file back."""
+    seek, buf = _seek_table(os.path.getsize(path) // 2)
+    nsym = ctypes.c_uint64()
+    check(load().hz_archive_file_seek(os.fsencode(path), int(verbose), buf.ctypes.data_as(ctypes.c_void_p), buf.size * 8,
+                                      ctypes.byref(nsym)), "hz_archive_file_seek")
+    return str(path) + ".compressed", seek[:seek_bytes(nsym.value) // 8]
+
+
+def archive_stream_seek(path, out_path, chunk_bytes=1 << 30, verbose=False):
+    """archive_stream() that returns the file's seek table, from the writer (chunks are rounded down
+    to whole 4096-byte blocks; the output does not depend on the chunk size)."""
+    seek, buf = _seek_table(os.path.getsize(path) // 2)
+    nsym = ctypes.c_uint64()
+    check(load().hz_archive_stream_seek(os.fsencode(path), os.fsencode(out_path), chunk_bytes, int(verbose),
+                                        buf.ctypes.data_as(ctypes.c_void_p), buf.size * 8, ctypes.byref(nsym)),
+          "hz_archive_stream_seek")
+    return seek[:seek_bytes(nsym.value) // 8]
 
 
 def extract_stream(path, out_path, chunk_bytes=1 << 30, verbose=False):
@@ -306,6 +350,14 @@ class Device:
     def pack_ranges(self, d_in, n, start_bit, lead, d_out, out_cap, d_index, d_ranges):
         check(self.lib.hz_pack_ranges(self.h, d_in, n, start_bit, lead, d_out, out_cap, d_index, d_ranges),
               "hz_pack_ranges")
+
+    def pack_seek(self, d_in, n, start_bit, lead, d_out, out_cap, d_seek, d_ranges=None, sym_base=0, bit_base=0,
+                  stream_nsym=None):
+        """pack (or, with d_ranges, pack_ranges) that also writes the call's seek entries into the stream's
+        table d_seek: the call covers symbols [sym_base, sym_base + n // 2) of a stream of stream_nsym
+        (default: n // 2); entries are bits from byte 0 of d_out plus bit_base. No block index."""
+        check(self.lib.hz_pack_seek(self.h, d_in, n, start_bit, lead, d_out, out_cap, d_ranges, sym_base, bit_base,
+                                    n // 2 if stream_nsym is None else stream_nsym, d_seek), "hz_pack_seek")
 
     def last_pack_ranges(self):
         """1 when the last pack_ranges took the range plan (no count pass), 0 for count + scan + write."""

@@ -404,8 +404,16 @@ static uint64_t clamp_reach(const hz_ctx* c, uint64_t payload_bytes, uint64_t st
     return nsym <= (UINT64_MAX - start_bit) / 64 && payload_bytes > reach ? reach : payload_bytes;
 }
 
+// hz_pack_seek's placement: the call packs symbols [sym_base, sym_base + n / 2) of a stream of stream_nsym
+// and writes their entries of the table at d_seek (addressed from entry 0), each counted bit_base
+// further than from byte 0 of d_out.
+struct PackSeek {
+    uint64_t sym_base, bit_base, stream_nsym;
+    uint64_t* d_seek;
+};
+
 static int pack_impl(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t start_bit, uint32_t lead, uint8_t* d_out,
-                     uint64_t out_cap, uint64_t* d_index, void* d_ranges) {
+                     uint64_t out_cap, uint64_t* d_index, void* d_ranges, const PackSeek* sk = nullptr) {
     if (!c || !d_out) return HZ_EINVAL;
     if (((uintptr_t)d_out) & 3) return HZ_EINVAL;
     const uint64_t nsym = n / 2;
@@ -418,6 +426,20 @@ static int pack_impl(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t start_
     HZ_TRY(hipSetDevice(c->device));
     int rc = ensure_scratch(c, pack_scratch_words(nsym));
     if (rc) return rc;
+    if (sk) {
+        // the writer waves store start[] of the call's blocks straight into its window of the table (the
+        // stream's end after the last block), then the window moves by bit_base; no scratch beyond the pack's
+        unsigned long long* win = reinterpret_cast<unsigned long long*>(sk->d_seek) + sk->sym_base / kBlockSyms;
+        return timed_stage(c, HZ_STAGE_PACK, "launch_pack (seek)", [&] {
+            hipError_t e = launch_pack(c->t, d_in, nsym, start_bit, lead, reinterpret_cast<uint32_t*>(d_out), out_cap / 4,
+                                       c->d_desc, win, c->d_err, c->ncu, c->stream, d_ranges, &c->last_pack_ranges, true);
+            if (e != hipSuccess) return e;
+            if (c->t.enc_mode == ENC_FIXED16)  // symbol i at start_bit + 16 i
+                return seek_fixed16(start_bit, nsym, UINT64_MAX, sk->sym_base, nsym, sk->stream_nsym, sk->bit_base,
+                                    reinterpret_cast<unsigned long long*>(sk->d_seek), c->stream);
+            return launch_seek_add(win, index_blocks(nsym) + 1, sk->bit_base, c->stream);
+        });
+    }
     return timed_stage(c, HZ_STAGE_PACK, "launch_pack", [&] {
         return launch_pack(c->t, d_in, nsym, start_bit, lead, reinterpret_cast<uint32_t*>(d_out), out_cap / 4,
                            c->d_desc, reinterpret_cast<unsigned long long*>(d_index), c->d_err, c->ncu, c->stream,
@@ -435,6 +457,21 @@ extern "C" int hz_pack_ranges(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64
     if (c) c->last_pack_ranges = 0;
     if (range_geom(n / 2).bytes && (!d_ranges || (((uintptr_t)d_ranges) & 15))) return HZ_EINVAL;
     return pack_impl(c, d_in, n, start_bit, lead, d_out, out_cap, d_index, range_geom(n / 2).bytes ? d_ranges : nullptr);
+}
+
+extern "C" int hz_pack_seek(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t start_bit, uint32_t lead, uint8_t* d_out,
+                            uint64_t out_cap, void* d_ranges, uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym,
+                            uint64_t* d_seek) {
+    if (c) c->last_pack_ranges = 0;
+    const uint64_t nsym = n / 2;
+    if (!d_seek || (((uintptr_t)d_seek) & 7)) return HZ_EINVAL;
+    if (sym_base % kBlockSyms || sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
+    // whole blocks, or the stream's last call: every entry of the window is a block start of this call
+    if (nsym % kBlockSyms && sym_base + nsym != stream_nsym) return HZ_EINVAL;
+    const bool plan = d_ranges && range_geom(nsym).bytes;
+    if (plan && (((uintptr_t)d_ranges) & 15)) return HZ_EINVAL;
+    const PackSeek sk{sym_base, bit_base, stream_nsym, d_seek};
+    return pack_impl(c, d_in, n, start_bit, lead, d_out, out_cap, nullptr, plan ? d_ranges : nullptr, &sk);
 }
 
 extern "C" int hz_last_pack_ranges(hz_ctx* c) { return c ? c->last_pack_ranges : 0; }

@@ -42,8 +42,10 @@ int plan_encode(const uint8_t* in, uint64_t n, hz_ctx** ctx, DevBuf& din, Encode
     return HZ_OK;
 }
 
-// Encode a host buffer into a complete .compressed image.
-int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint32_t* nsym_out) {
+// Encode a host buffer into a complete .compressed image. seek (nullable): the image's seek table from the
+// writer (hz_pack_seek), hz_seek_bytes(n / 2) bytes: the pack's output starts at the file byte of the first
+// payload bit, which is where the table's bits count from.
+int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint32_t* nsym_out, uint64_t* seek = nullptr) {
     hz_ctx* c;
     DevBuf din;
     EncodePlan p;
@@ -66,12 +68,19 @@ int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint3
         const uint64_t start_bit = pend_bits;
         const uint64_t pay_bytes = file_bytes - hbytes_full;
         const uint64_t words = (start_bit + p.payload_bits + 31) / 32;
-        DevBuf dout;
+        DevBuf dout, dseek;
         if ((rc = dout.alloc(words * 4))) return rc;
-        if ((rc = hz_pack(c, (const uint8_t*)din.p, n, start_bit, (uint32_t)(pend >> (8 - pend_bits)) * (pend_bits ? 1 : 0),
-                          (uint8_t*)dout.p, words * 4, nullptr)))
-            return rc;
+        const uint32_t lead = (uint32_t)(pend >> (8 - pend_bits)) * (pend_bits ? 1 : 0);
+        if (seek) {
+            if ((rc = dseek.alloc(hz_seek_bytes(nsym)))) return rc;
+            rc = hz_pack_seek(c, (const uint8_t*)din.p, n, start_bit, lead, (uint8_t*)dout.p, words * 4, nullptr, 0, 0, nsym,
+                              (uint64_t*)dseek.p);
+        } else {
+            rc = hz_pack(c, (const uint8_t*)din.p, n, start_bit, lead, (uint8_t*)dout.p, words * 4, nullptr);
+        }
+        if (rc) return rc;
         HZ_TRY(hipMemcpyAsync(out.data() + hbytes_full, dout.p, pay_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (seek) HZ_TRY(hipMemcpyAsync(seek, dseek.p, hz_seek_bytes(nsym), hipMemcpyDeviceToHost, c->stream));
         if ((rc = hz_ctx_sync(c))) return rc;
     } else if (pend_bits) {
         out[hbytes_full] = pend;  // unreachable (header is byte aligned without symbols) but kept exact
@@ -338,6 +347,17 @@ extern "C" int hz_encode_host(const uint8_t* in, uint64_t n, uint8_t* out, uint6
     return guarded([&]() -> int {
         std::vector<uint8_t> img;  // (never empty: the header alone is 11 bytes)
         const int rc = encode_image(in, n, img, nullptr);
+        return rc ? rc : give(img, out, cap, out_len);
+    });
+}
+
+extern "C" int hz_encode_host_seek(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len,
+                                   uint64_t* seek, uint64_t seek_cap_bytes) {
+    if ((!in && n) || !out_len) return HZ_EINVAL;
+    if (seek_cap_bytes < hz_seek_bytes(n / 2) || (!seek && n / 2)) return HZ_ECAP;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> img;
+        const int rc = encode_image(in, n, img, nullptr, seek);
         return rc ? rc : give(img, out, cap, out_len);
     });
 }

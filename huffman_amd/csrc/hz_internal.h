@@ -316,7 +316,10 @@ hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long l
 hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint64_t start_bit,
                        uint32_t lead, uint32_t* d_out, uint64_t out_words, unsigned long long* d_scratch,
                        unsigned long long* d_index, uint32_t* d_err, int ncu, hipStream_t s,
-                       void* d_ranges = nullptr, int* used_ranges = nullptr);
+                       void* d_ranges = nullptr, int* used_ranges = nullptr,
+                       bool seek = false);  // d_index is start[] alone: nblocks + 1 words, no max_bits, no sub[]
+                                            // (FIXED16: not written, its table is arithmetic -- seek_fixed16)
+hipError_t launch_seek_add(unsigned long long* d, uint64_t n, uint64_t add, hipStream_t s);  // d[0..n) += add
 uint64_t pack_scratch_words(uint64_t nsym);  // u64 words of d_scratch hz_pack needs
 // Table uploads: segments of a pinned host staging buffer copied to their device tables by one kernel
 // (it reads the host memory over PCIe: one launch per upload instead of one copy per table).

@@ -452,6 +452,9 @@ struct PackOut {
     uint32_t sh4, nwords;
 };
 
+// SEEK (hz_pack_seek): a.index holds start[] alone -- the block's start bit and nothing else is stored
+// (no sub[] row), and the existing instances compile as before.
+template <bool SEEK = false>
 HZ_DEV void pack_copyout(const PackArgs& a, const uint32_t* slot, int lane, const PackOut& p) {
     if (!p.pending) return;
     if (p.fits) {
@@ -480,7 +483,9 @@ HZ_DEV void pack_copyout(const PackArgs& a, const uint32_t* slot, int lane, cons
             a.out[p.base4 + i] = bswap32(slot[i]);
         }
     }
-    if (a.index) {
+    if constexpr (SEEK) {
+        if (lane == 0) a.index[p.blk] = p.bstart;
+    } else if (a.index) {
         a.index_sub[p.blk * kWave + lane] = p.sub;
         if (lane == 0) a.index[p.blk] = p.bstart;
     }
@@ -551,8 +556,9 @@ HZ_DEV uint32_t pack_own_tail(const PackBlk<MODE>& b) {
 // has checked that the block goes through the wave's LDS slot (not the last block, fits the slot), so
 // the direct path is not compiled in. CARRY (with SLOT_ONLY): *tail holds the 32 bits before the
 // block (b.pe is not read) and returns the block's own last 32 bits -- the low word of lane 63's
-// accumulator, since every lane holds 32 codes of >= 1 bit.
-template <int MODE, bool SLOT_ONLY = false, bool CARRY = false>
+// accumulator, since every lane holds 32 codes of >= 1 bit. SEEK: the index is start[] alone (the
+// block's start bit, the stream's end after the last block; no sub[] row, no max_bits).
+template <int MODE, bool SLOT_ONLY = false, bool CARRY = false, bool SEEK = false>
 HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int lane, const PackBlk<MODE>& b,
                             uint64_t bstart, uint64_t& max_bits, PackOut* defer = nullptr, uint32_t* tail = nullptr) {
     static_assert(!CARRY || (SLOT_ONLY && MODE != ENC_WIDE), "the carried tail is the slot path's");
@@ -602,12 +608,14 @@ HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int
             defer->nwords = nwords;
             defer->blk = blk;
             defer->bstart = bstart;
-            uint64_t sub = 0;
+            if constexpr (!SEEK) {
+                uint64_t sub = 0;
 #pragma unroll
-            for (int c = 0; c < kChainsPerLane; ++c)
-                sub |= (uint64_t)(((uint32_t)bstart + ex_n + b.nc[c]) & 0xffffu) << (16 * c);
-            defer->sub = sub;
-            max_bits = b.bits > max_bits ? b.bits : max_bits;
+                for (int c = 0; c < kChainsPerLane; ++c)
+                    sub |= (uint64_t)(((uint32_t)bstart + ex_n + b.nc[c]) & 0xffffu) << (16 * c);
+                defer->sub = sub;
+                max_bits = b.bits > max_bits ? b.bits : max_bits;
+            }
             return;
         }
         if (fits) {
@@ -671,7 +679,12 @@ HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int
         if (fits && b.nvalid > 0 && sym0 + (uint64_t)b.nvalid == a.nsym && na > 0)
             *dst = bswap32((uint32_t)(acc << (32 - na)));
     }
-    if (a.index) {  // block index (hz_internal.h): start bits + the lane's chain offsets
+    if constexpr (SEEK) {
+        if (lane == 0) {
+            a.index[blk] = bstart;
+            if (last) a.index[a.nblocks] = bend;
+        }
+    } else if (a.index) {  // block index (hz_internal.h): start bits + the lane's chain offsets
         uint64_t sub = 0;
 #pragma unroll
         for (int c = 0; c < kChainsPerLane; ++c)
@@ -690,8 +703,10 @@ HZ_DEV void pack_block_emit(const PackArgs& a, uint32_t* slot, uint64_t blk, int
 // k_pack_count + k_scan_*; wave w packs blocks w, w + W, ...) or, RNG, the
 // range plan (after k_range_dot + k_range_scan; wave w packs the blocks of
 // ranges w, w + W, ... in order, each block starting where the one before it
-// ended: a running sum, no count pass).
-template <int MODE, bool RNG, bool SPLIT>
+// ended: a running sum, no count pass). SEEK (hz_pack_seek): instances of their own that store the
+// seek table -- a.index is start[] alone, written by the wave that holds each block's start bit (the
+// range plan has no blk_start array to copy from); the instances without it are the code they were.
+template <int MODE, bool RNG, bool SPLIT, bool SEEK = false>
 __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     if constexpr (MODE != ENC_WIDE) copy_lds_table(lds, a.lds_img, a.lds_words);
@@ -770,7 +785,7 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
             hot_issue<true, !kCarry>(a, nx.raw, nx.psym, hl);  // block k+1 (past the wave's end: a repeat, unused)
             __builtin_amdgcn_s_setprio(0);
             const uint64_t nbst = nx.bstart;
-            pack_copyout(a, slot, lane, po);  // block k-1's stores, behind the escape loads
+            pack_copyout<SEEK>(a, slot, lane, po);  // block k-1's stores, behind the escape loads
             po.pending = false;
             const uint64_t pb = nnb < a.nblocks ? nnb : (nb < a.nblocks ? nb : blk);
             pack_prefetch<!kCarry>(a, pb, lane, nx);
@@ -787,9 +802,9 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
                 if constexpr (kCarry) tail = pack_own_tail<MODE>(b);
             } else if constexpr (kCarry) {
                 if (!have_tail) tail = hot_prev_tail(a, blk, lane);  // the first block of a range
-                pack_block_emit<MODE, true, true>(a, slot, blk, lane, b, bst, max_bits, &po, &tail);
+                pack_block_emit<MODE, true, true, SEEK>(a, slot, blk, lane, b, bst, max_bits, &po, &tail);
             } else {
-                pack_block_emit<MODE, true>(a, slot, blk, lane, b, bst, max_bits, &po);
+                pack_block_emit<MODE, true, false, SEEK>(a, slot, blk, lane, b, bst, max_bits, &po);
             }
             have_tail = !nb_newr;
             if (RNG) run = nb_newr ? nb_run : run + b.bits;
@@ -799,8 +814,8 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
             nb_newr = nn_newr;
             nb_run = nn_run;
         }
-        pack_copyout(a, slot, lane, po);
-        if (a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
+        pack_copyout<SEEK>(a, slot, lane, po);
+        if (!SEEK && a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
         return;
     }
     PackIn nx;  // the next block's inputs, in flight while this block is packed
@@ -822,7 +837,7 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
         PackIn cur = nx;
         PackBlk<MODE> b;
         // the previous block's stores go out behind this block's escape loads
-        pack_block_lookup<MODE, kSplit>(a, lds, blk, lane, cur, b, [&]() { pack_copyout(a, slot, lane, po); });
+        pack_block_lookup<MODE, kSplit>(a, lds, blk, lane, cur, b, [&]() { pack_copyout<SEEK>(a, slot, lane, po); });
         po.pending = false;
         // next block's loads: after this block's escapes, so no wait covers them early
         pack_prefetch(a, nb < a.nblocks ? nb : blk, lane, nx);
@@ -838,22 +853,22 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_write(PackArgs a) {
                     a.cold[2 + 2 * i] = bst;
                 }
             } else {
-                pack_block_emit<MODE, true>(a, slot, blk, lane, b, bst, max_bits, &po);
+                pack_block_emit<MODE, true, false, SEEK>(a, slot, blk, lane, b, bst, max_bits, &po);
             }
         } else {
-            pack_block_emit<MODE>(a, slot, blk, lane, b, bst, max_bits, &po);
+            pack_block_emit<MODE, false, false, SEEK>(a, slot, blk, lane, b, bst, max_bits, &po);
         }
         if (RNG) run = newr ? nrun : run + b.bits;
         blk = nb;
     }
-    pack_copyout(a, slot, lane, po);
-    if (a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
+    pack_copyout<SEEK>(a, slot, lane, po);
+    if (!SEEK && a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
 }
 
 // The blocks k_pack_write listed in a.cold (the stream's last block, which may be partial, and blocks
 // larger than a wave's LDS slot): per-symbol masked lookups, each lane's codes stored straight to the
 // output, the index entries. Usually one block; workgroups past the list leave before loading the table.
-template <int MODE>
+template <int MODE, bool SEEK = false>
 __global__ __launch_bounds__(kPackWriteThreads) void k_pack_cold(PackArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint64_t n = a.cold[0];
@@ -869,9 +884,9 @@ __global__ __launch_bounds__(kPackWriteThreads) void k_pack_cold(PackArgs a) {
         PackBlk<MODE> b;
         pack_block_lookup<MODE>(a, lds, blk, lane, in, b);
         pack_block_count<MODE>(lane, b);
-        pack_block_emit<MODE>(a, nullptr, blk, lane, b, bst, max_bits, nullptr);
+        pack_block_emit<MODE, false, false, SEEK>(a, nullptr, blk, lane, b, bst, max_bits, nullptr);
     }
-    if (a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
+    if (!SEEK && a.index && lane == 0 && max_bits) atomicMax(a.index + a.nblocks + 1, (unsigned long long)max_bits);
 }
 
 // ---- every code 16 bits (U = 65 536, min_len = max_len = 16) ---------------
@@ -1174,13 +1189,24 @@ uint64_t pack_scratch_words(uint64_t nsym) {
 // The k_pack_write instance: SPLIT (cold blocks to k_pack_cold) for HOT, and for DENSE when the
 // workgroup has output slots; WIDE and a slot-less DENSE keep the direct path in the loop (split,
 // every block of a slot-less pack would be looked up twice).
-static const void* pack_write_fn(int mode, bool rng, bool split) {
-    if (mode == ENC_HOT) return rng ? (const void*)k_pack_write<ENC_HOT, true, true> : (const void*)k_pack_write<ENC_HOT, false, true>;
+template <bool SEEK>
+static const void* pack_write_inst(int mode, bool rng, bool split) {
+    if (mode == ENC_HOT)
+        return rng ? (const void*)k_pack_write<ENC_HOT, true, true, SEEK> : (const void*)k_pack_write<ENC_HOT, false, true, SEEK>;
     if (mode == ENC_DENSE) {
-        if (split) return rng ? (const void*)k_pack_write<ENC_DENSE, true, true> : (const void*)k_pack_write<ENC_DENSE, false, true>;
-        return rng ? (const void*)k_pack_write<ENC_DENSE, true, false> : (const void*)k_pack_write<ENC_DENSE, false, false>;
+        if (split)
+            return rng ? (const void*)k_pack_write<ENC_DENSE, true, true, SEEK>
+                       : (const void*)k_pack_write<ENC_DENSE, false, true, SEEK>;
+        return rng ? (const void*)k_pack_write<ENC_DENSE, true, false, SEEK> : (const void*)k_pack_write<ENC_DENSE, false, false, SEEK>;
     }
-    return rng ? (const void*)k_pack_write<ENC_WIDE, true, false> : (const void*)k_pack_write<ENC_WIDE, false, false>;
+    return rng ? (const void*)k_pack_write<ENC_WIDE, true, false, SEEK> : (const void*)k_pack_write<ENC_WIDE, false, false, SEEK>;
+}
+static const void* pack_write_fn(int mode, bool rng, bool split, bool seek) {
+    return seek ? pack_write_inst<true>(mode, rng, split) : pack_write_inst<false>(mode, rng, split);
+}
+static const void* pack_cold_fn(int mode, bool seek) {
+    if (mode == ENC_DENSE) return seek ? (const void*)k_pack_cold<ENC_DENSE, true> : (const void*)k_pack_cold<ENC_DENSE>;
+    return seek ? (const void*)k_pack_cold<ENC_HOT, true> : (const void*)k_pack_cold<ENC_HOT>;
 }
 static hipError_t pack_write_launch(const void* fn, uint64_t grid, int threads, uint32_t lds, hipStream_t s, PackArgs a) {
     void* args[] = {&a};
@@ -1191,21 +1217,19 @@ static hipError_t pack_write_launch(const void* fn, uint64_t grid, int threads, 
 static hipError_t pack_cold_reset(const PackArgs& a, hipStream_t s) {
     return hipMemsetAsync(a.cold, 0, sizeof(unsigned long long), s);
 }
-static void pack_cold_launch(const Tables& t, const PackArgs& a, uint32_t lds, int ncu, hipStream_t s) {
+static void pack_cold_launch(const Tables& t, const PackArgs& a, uint32_t lds, int ncu, hipStream_t s, bool seek) {
     const uint64_t waves = kPackWriteThreads / 64;
     uint64_t g = (a.nblocks + waves - 1) / waves;
     if (g > (uint64_t)ncu) g = ncu;  // table-sized LDS: one workgroup per CU
-    switch (t.enc_mode) {
-        case ENC_DENSE: hipLaunchKernelGGL(k_pack_cold<ENC_DENSE>, dim3(g), dim3(kPackWriteThreads), lds, s, a); break;
-        case ENC_HOT: hipLaunchKernelGGL(k_pack_cold<ENC_HOT>, dim3(g), dim3(kPackWriteThreads), lds, s, a); break;
-        default: break;  // WIDE keeps the direct path inside k_pack_write
-    }
+    // (WIDE keeps the direct path inside k_pack_write)
+    if (t.enc_mode == ENC_DENSE || t.enc_mode == ENC_HOT)
+        (void)pack_write_launch(pack_cold_fn(t.enc_mode, seek), g, kPackWriteThreads, lds, s, a);
 }
 
 hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint64_t start_bit, uint32_t lead,
                        uint32_t* d_out, uint64_t out_words, unsigned long long* d_scratch,
                        unsigned long long* d_index, uint32_t* d_err, int ncu, hipStream_t s, void* d_ranges,
-                       int* used_ranges) {
+                       int* used_ranges, bool seek) {
     if (used_ranges) *used_ranges = 0;
     if (nsym == 0) return hipSuccess;
     const uint64_t nblocks = (nsym + kBlockSyms - 1) / kBlockSyms;
@@ -1220,10 +1244,13 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
     unsigned long long* blk_start = d_scratch + nblocks;
     unsigned long long* tiles = d_scratch + 2 * nblocks;
     a.blk_start = blk_start; a.index = d_index; a.err = d_err;
-    a.index_sub = d_index ? d_index + index_sub_offset(nblocks) : nullptr;
+    a.index_sub = d_index && !seek ? d_index + index_sub_offset(nblocks) : nullptr;
+    // seek: d_index is start[] alone (nblocks + 1 words). Every code of a FIXED16 stream starts at
+    // start_bit + 16 i: the caller writes that table without the kernels (seek_fixed16)
+    if (seek && t.enc_mode == ENC_FIXED16) a.index = nullptr;
     a.rstart = nullptr; a.bpr = 0; a.nranges = 0;
     a.cold = tiles + ntiles;
-    if (d_index && t.enc_mode != ENC_FIXED16) {
+    if (d_index && !seek && t.enc_mode != ENC_FIXED16) {
         hipError_t e = hipMemsetAsync(d_index + nblocks + 1, 0, 8, s);  // max_bits, raised per block
         if (e != hipSuccess) return e;
     }
@@ -1272,8 +1299,7 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
     // k_pack_write leaves its cold blocks to k_pack_cold (HOT always has slots: mean code <= 17 bits)
     const bool split = t.enc_mode == ENC_HOT || (t.enc_mode == ENC_DENSE && a.slot_words > 0);
     if (split) {
-        const void* fc = t.enc_mode == ENC_DENSE ? (const void*)k_pack_cold<ENC_DENSE> : (const void*)k_pack_cold<ENC_HOT>;
-        hipError_t e = ensure_lds_limit(fc, kLdsBytes);
+        hipError_t e = ensure_lds_limit(pack_cold_fn(t.enc_mode, seek), kLdsBytes);
         if (e != hipSuccess) return e;
         if ((e = pack_cold_reset(a, s)) != hipSuccess) return e;
     }
@@ -1283,7 +1309,7 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
         if (rw > cap) rw = cap;
         const uint64_t W = rw * waves;
         if (W >= g.nranges || g.nranges % W == 0) {
-            const void* fr = pack_write_fn(t.enc_mode, true, split);
+            const void* fr = pack_write_fn(t.enc_mode, true, split, seek);
             hipError_t e = ensure_lds_limit(fr, kLdsBytes);
             if (e != hipSuccess) return e;
             const RangeArgs r = range_args(d_ranges, g, d_err);
@@ -1292,7 +1318,7 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
             hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(kScanThreads), 0, s, r, start_bit);
             a.rstart = r.start; a.bpr = g.bpr; a.nranges = g.nranges; a.blk_start = nullptr;
             if ((e = pack_write_launch(fr, rw, threads, lds, s, a)) != hipSuccess) return e;
-            if (split) pack_cold_launch(t, a, 4 * table_words, ncu, s);
+            if (split) pack_cold_launch(t, a, 4 * table_words, ncu, s, seek);
             if (used_ranges) *used_ranges = 1;
             return hipGetLastError();
         }
@@ -1300,7 +1326,7 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
     {
         hipError_t e = ensure_lds_limit((const void*)k_pack_count, kLen8LdsBytes);
         if (e != hipSuccess) return e;
-        if ((e = ensure_lds_limit(pack_write_fn(t.enc_mode, false, split), kLdsBytes)) != hipSuccess) return e;
+        if ((e = ensure_lds_limit(pack_write_fn(t.enc_mode, false, split, seek), kLdsBytes)) != hipSuccess) return e;
     }
     {
         const uint64_t cw = kCountThreads / 64;
@@ -1311,9 +1337,22 @@ hipError_t launch_pack(const Tables& t, const uint8_t* d_in, uint64_t nsym, uint
     {
         hipError_t e = launch_scan(a.blk, nblocks, tiles, blk_start, 0xffffffffull, start_bit, s);
         if (e != hipSuccess) return e;
-        if ((e = pack_write_launch(pack_write_fn(t.enc_mode, false, split), wgs, threads, lds, s, a)) != hipSuccess) return e;
+        if ((e = pack_write_launch(pack_write_fn(t.enc_mode, false, split, seek), wgs, threads, lds, s, a)) != hipSuccess) return e;
     }
-    if (split) pack_cold_launch(t, a, 4 * table_words, ncu, s);
+    if (split) pack_cold_launch(t, a, 4 * table_words, ncu, s, seek);
+    return hipGetLastError();
+}
+
+// hz_pack_seek's placement: the n entries at d (the call's window of the stream's table) count from
+// byte 0 of the call's output; the table counts bit_base further.
+__global__ __launch_bounds__(256) void k_seek_add(unsigned long long* d, uint64_t n, uint64_t add) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) d[i] += add;
+}
+
+hipError_t launch_seek_add(unsigned long long* d, uint64_t n, uint64_t add, hipStream_t s) {
+    if (n == 0 || add == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_seek_add, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d, n, add);
     return hipGetLastError();
 }
 

@@ -264,16 +264,35 @@ extern "C" int hz_stream_last_timing(hz_stream_timing* t) {
     return HZ_OK;
 }
 
+// Where a streamed call leaves the file's seek table (hz_archive_stream_seek, hz_extract_stream_seek).
+struct SeekSink {
+    uint64_t* seek;      // host, cap_bytes
+    uint64_t cap_bytes;
+    uint64_t* nsym;      // out: the file's symbols
+};
+
 // resident: keep the input on the device after pass 1 when the file fits
 // (hz_archive_file; Compressor.cu:324-367 reads the file once into pinned
 // memory), so pass 2 packs it in one launch without reading the file again.
+//
+// With a SeekSink the writer also leaves the file's seek table (hz_archive_stream_seek): every pack is
+// hz_pack_seek at sym_base = the symbols packed and bit_base = 8 x the payload bytes handed to the file
+// writer (the pack's output starts at the file byte of the first payload bit, which is where the table's
+// bits count from), into one device table copied out once at the end. Chunks are whole blocks, and a
+// chunk's end bit comes back from the table: no per-chunk block index.
 static int hz_archive_stream_impl(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
-                                  bool resident) {
+                                  bool resident, const SeekSink* sink = nullptr) {
     if (!in_path || !out_path || chunk_bytes < 64) return HZ_EINVAL;
+    if (sink && !sink->nsym) return HZ_EINVAL;
     chunk_bytes &= ~(uint64_t)15;  // even (whole symbols) and 16-byte aligned device reads
+    if (sink) chunk_bytes = std::max<uint64_t>(chunk_bytes / (2 * kBlockSyms) * (2 * kBlockSyms), 2 * kBlockSyms);
     struct stat st;
     if (stat(in_path, &st) != 0) return HZ_ENOENT;
     const uint64_t n = (uint64_t)st.st_size;
+    if (sink) {
+        *sink->nsym = n / 2;
+        if (sink->cap_bytes < hz_seek_bytes(n / 2) || (!sink->seek && n / 2)) return HZ_ECAP;
+    }
     hz_ctx* c;
     const auto tc = Clock::now();
     int rc = default_ctx(&c);
@@ -400,7 +419,8 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
     const uint64_t nsym_total = n / 2;
     const uint64_t body = 2 * nsym_total;  // the odd last byte travels in the header
     uint32_t lead = pend_bits ? (uint32_t)(pend >> (8 - pend_bits)) : 0u;
-    DevBuf dpay;
+    DevBuf dpay, dseek;
+    if (sink && nsym_total && (rc = dseek.alloc(hz_seek_bytes(nsym_total)))) return rc;
     if (resident && nsym_total) {
         const uint64_t pay_bytes = (pend_bits + pbits + 7) / 8;
         const uint64_t cap = ((pend_bits + pbits + 31) / 32 + 1) * 4;
@@ -414,8 +434,10 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
             if ((rc = hz_codebook_upload_encode(c, cb.get()))) return rc;
             g_timing.host_ms += ms_since(tu);
             hipEvent_t t1 = spans.mark(c->stream);
-            if ((rc = hz_pack(c, (const uint8_t*)dall.p, body, pend_bits, lead, (uint8_t*)dpay.p, cap, nullptr)))
-                return rc;
+            rc = sink ? hz_pack_seek(c, (const uint8_t*)dall.p, body, pend_bits, lead, (uint8_t*)dpay.p, cap, nullptr, 0, 0,
+                                     nsym_total, (uint64_t*)dseek.p)
+                      : hz_pack(c, (const uint8_t*)dall.p, body, pend_bits, lead, (uint8_t*)dpay.p, cap, nullptr);
+            if (rc) return rc;
             spans.add(t1, spans.mark(c->stream), &g_timing.kernel_ms);
             for (uint64_t off = 0, k = 0; off < pay_bytes; off += chunk, ++k) {
                 const int b = (int)(k & 1);
@@ -454,7 +476,7 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
             if ((rc = dout[i].alloc(out_cap))) return rc;
             if ((rc = hout[i].alloc(out_cap))) return rc;
         }
-        if ((rc = didx.alloc(hz_index_bytes(csym)))) return rc;
+        if (!sink && (rc = didx.alloc(hz_index_bytes(csym)))) return rc;
         g_timing.alloc_ms += ms_since(tb);
         WriterDrain wdrain{fout};
         DrainGuard drain_out(c->stream);
@@ -467,6 +489,7 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
         if ((rc = read_exact(fp, hin[0].p, std::min(chunk, body)))) return rc;
         int wbuf = -1;          // chunk waiting for its write: buffer, bytes
         uint64_t wbytes = 0;
+        uint64_t emitted = 0;   // payload bytes of the chunks before this one
         for (uint64_t off = 0, k = 0; off < body; off += chunk, ++k) {
             const int b = (int)(k & 1);
             const uint64_t len = std::min(chunk, body - off);
@@ -475,14 +498,17 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
             spans.add(t0, spans.mark(c->stream), &g_timing.h2d_ms);
             if (k >= 2) HZ_TRY(hipStreamWaitEvent(c->stream, copied.e[b], 0));  // dout[b] copied out
             hipEvent_t t1 = spans.mark(c->stream);
-            if ((rc = hz_pack(c, (const uint8_t*)din[b].p, len, sbit, lead, (uint8_t*)dout[b].p, out_cap,
-                              (uint64_t*)didx.p)))
-                return rc;
+            rc = sink ? hz_pack_seek(c, (const uint8_t*)din[b].p, len, sbit, lead, (uint8_t*)dout[b].p, out_cap, nullptr,
+                                     off / 2, 8 * emitted, nsym_total, (uint64_t*)dseek.p)
+                      : hz_pack(c, (const uint8_t*)din[b].p, len, sbit, lead, (uint8_t*)dout[b].p, out_cap, (uint64_t*)didx.p);
+            if (rc) return rc;
             spans.add(t1, spans.mark(c->stream), &g_timing.kernel_ms);
             HZ_TRY(hipEventRecord(packed.e[b], c->stream));
             const uint64_t nb = (len / 2 + 2047) / 2048;
             uint64_t end_bit = 0;
-            HZ_TRY(hipMemcpyAsync(&end_bit, (const uint64_t*)didx.p + nb, 8, hipMemcpyDeviceToHost, c->stream));
+            // the chunk's end: the index's last start[] word or, in the table, the entry after its last block
+            const uint64_t* d_end = sink ? (const uint64_t*)dseek.p + off / 2 / kBlockSyms + nb : (const uint64_t*)didx.p + nb;
+            HZ_TRY(hipMemcpyAsync(&end_bit, d_end, 8, hipMemcpyDeviceToHost, c->stream));
             // host work beside the upload and pack: the previous chunk's write, the next chunk's fread
             if (wbuf >= 0) {
                 HZ_TRY(hipEventSynchronize(copied.e[wbuf]));
@@ -495,6 +521,7 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
             if (next < body && (rc = read_exact(fp, hin[1 - b].p, std::min(chunk, body - next)))) return rc;
             if ((rc = hz_ctx_sync(c))) return rc;
             spans.fold();
+            if (sink) end_bit -= 8 * emitted;  // the table counts from the payload's first byte
             const bool last = next >= body;
             const uint64_t bytes = last ? (end_bit + 7) / 8 : end_bit / 32 * 4;  // complete words until the end
             sbit = (uint32_t)(end_bit % 32);
@@ -513,6 +540,7 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
             HZ_TRY(hipEventRecord(copied.e[b], cs.s));
             wbuf = b;
             wbytes = bytes;
+            emitted += bytes;
         }
         if (wbuf >= 0) {
             HZ_TRY(hipEventSynchronize(copied.e[wbuf]));
@@ -522,6 +550,12 @@ static int hz_archive_stream_impl(const char* in_path, const char* out_path, uin
         }
         if ((rc = fout.wait())) return rc;
         HZ_TRY(hipStreamSynchronize(cs.s));
+    }
+    if (sink && nsym_total) {  // the table, once
+        hipEvent_t t3 = spans.mark(c->stream);
+        HZ_TRY(hipMemcpyAsync(sink->seek, dseek.p, hz_seek_bytes(nsym_total), hipMemcpyDeviceToHost, c->stream));
+        spans.add(t3, spans.mark(c->stream), &g_timing.d2h_ms);
+        if ((rc = hz_ctx_sync(c))) return rc;
     }
     if ((rc = fout.close())) return rc;
     spans.fold();
@@ -602,12 +636,6 @@ static int parse_header_for_extract(const std::vector<uint8_t>& head, hz_codeboo
 // earlier rounds consumed, into one device table copied out once at the end. A round redone after an
 // overrun rewrites its entries, and later rounds overwrite what the overrun attempt wrote past its
 // window. Without an out_path (sink only) nothing is decoded, copied out or written.
-struct SeekSink {
-    uint64_t* seek;      // host, cap_bytes
-    uint64_t cap_bytes;
-    uint64_t* nsym;      // out: the file's symbols
-};
-
 static int hz_extract_stream_impl(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
                                   const SeekSink* sink = nullptr) {
     if (!in_path || (!out_path && !sink) || chunk_bytes < 4096) return HZ_EINVAL;
@@ -795,8 +823,14 @@ extern "C" int hz_extract_stream_seek(const char* in_path, const char* out_path,
     return timed_call([&] { return hz_extract_stream_impl(in_path, out_path, chunk_bytes, verbose, &sink); });
 }
 
-// Compressor.cu:315-632, stdout lines kept (:335-336,385,612-631).
-extern "C" int hz_archive_file(const char* path, int verbose) {
+extern "C" int hz_archive_stream_seek(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
+                                      uint64_t* seek, uint64_t seek_cap_bytes, uint64_t* nsym) {
+    if (!nsym) return HZ_EINVAL;
+    const SeekSink sink{seek, seek_cap_bytes, nsym};
+    return timed_call([&] { return hz_archive_stream_impl(in_path, out_path, chunk_bytes, verbose, false, &sink); });
+}
+
+static int archive_file_impl(const char* path, int verbose, const SeekSink* sink) {
     if (!path) return HZ_EINVAL;
     struct stat st;
     if (stat(path, &st) != 0) {
@@ -807,13 +841,26 @@ extern "C" int hz_archive_file(const char* path, int verbose) {
     // HZ_ARCHIVE_CHUNK: chunk bytes of the file reads and payload writes (tests use small ones)
     const char* ce = getenv("HZ_ARCHIVE_CHUNK");
     const uint64_t chunk = ce && strtoull(ce, nullptr, 10) >= 64 ? strtoull(ce, nullptr, 10) : kArchiveChunk;
+    if (sink) {  // a table too small is refused here: whatever stands at outname stays as it is
+        *sink->nsym = (uint64_t)st.st_size / 2;
+        if (sink->cap_bytes < hz_seek_bytes(*sink->nsym) || (!sink->seek && *sink->nsym)) return HZ_ECAP;
+    }
     // resident: the input stays on the device between the passes when it fits
-    const int rc = timed_call([&] { return hz_archive_stream_impl(path, outname.c_str(), chunk, verbose, true); });
+    const int rc = timed_call([&] { return hz_archive_stream_impl(path, outname.c_str(), chunk, verbose, true, sink); });
     if (rc) {
         remove(outname.c_str());  // never leave a truncated archive behind
         if (verbose) std::cerr << "archive: " << hz_strerror(rc) << std::endl;
     }
     return rc;
+}
+
+// Compressor.cu:315-632, stdout lines kept (:335-336,385,612-631).
+extern "C" int hz_archive_file(const char* path, int verbose) { return archive_file_impl(path, verbose, nullptr); }
+
+extern "C" int hz_archive_file_seek(const char* path, int verbose, uint64_t* seek, uint64_t seek_cap_bytes, uint64_t* nsym) {
+    if (!nsym) return HZ_EINVAL;
+    const SeekSink sink{seek, seek_cap_bytes, nsym};
+    return archive_file_impl(path, verbose, &sink);
 }
 
 // Decompressor.cu:47-114.

@@ -151,6 +151,26 @@ class StreamCodec:
             self.dev.pack(x.data_ptr(), x.numel(), plan.start_bit, plan.lead, out.data_ptr(), out.numel(), iptr)
         return out
 
+    def pack_seek(self, x, plan, out, seek, sym_base=0, bit_base=0, stream_nsym=None):
+        """pack() that writes the stream's seek table instead of a block index: the start bit of every
+        block, known to the writer while it packs (hz_pack_seek). The range plan is used under pack()'s
+        identity rule. seek: an int64 device tensor of seek_bytes(stream_nsym) // 8 entries, the table of
+        the whole stream; this call covers symbols [sym_base, sym_base + x.numel() // 2) of its stream_nsym
+        (default: the call's own) and writes their entries, bits from byte 0 of `out` plus bit_base."""
+        nsym = x.numel() // 2
+        total = nsym if stream_nsym is None else stream_nsym
+        if seek.dtype != torch.int64 or not seek.is_contiguous() or seek.numel() < seek_bytes(total) // 8:
+            raise ValueError("seek: a contiguous int64 tensor of seek_bytes(stream_nsym) // 8 entries")
+        if x.data_ptr() % 16:
+            x = x.clone()  # as pack(): 16-byte vector reads, and no range plan to match
+        ranges = None
+        if self._ranges_of is not None and self._ranges_of == self._ident(x):
+            self._ranges_of = None
+            ranges = self.ranges.data_ptr()
+        self.dev.pack_seek(x.data_ptr(), x.numel(), plan.start_bit, plan.lead, out.data_ptr(), out.numel(),
+                           seek.data_ptr(), ranges, sym_base, bit_base, total)
+        return seek
+
     def decode(self, payload, nsym, index, out):
         self.dev.decode(payload.data_ptr(), payload.numel(), nsym, index.data_ptr(), out.data_ptr())
         return out

@@ -395,6 +395,31 @@ int hz_decode_indexless_seek(hz_ctx *ctx, const uint8_t *d_payload, uint64_t pay
                              uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym, uint64_t *d_seek);
 int hz_indexless_seek(hz_ctx *ctx, uint64_t sym_base, uint64_t nsym, uint64_t stream_nsym, uint64_t *d_seek);
 
+/* ---- the seek table from the writer ----------------------------------------
+ * The pack holds every block's start bit while it writes, so the table is a
+ * by-product of the encode: no walk of the finished stream and no full block
+ * index (520 bytes per block to keep 8 of them).
+ *
+ * hz_pack_seek: hz_pack (d_ranges NULL) or hz_pack_ranges (d_ranges non-null and
+ * hz_ranges_bytes(n) != 0; same fallback, same hz_last_pack_ranges) with the same
+ * arguments and the same bytes at d_out, that also writes the call's seek entries
+ * under the placement rule of hz_decode_indexless_seek. The call covers symbols
+ * [sym_base, sym_base + n / 2) of a stream of stream_nsym symbols: it writes
+ * d_seek[b], addressed from entry 0 of the stream's table, for every b with
+ * sym_base <= s_b <= sym_base + n / 2; the value is the block's start bit counted
+ * from byte 0 of d_out, plus bit_base, and for s_b = sym_base + n / 2 the call's
+ * end bit. Two adjacent calls both write their shared boundary, with equal
+ * values. Nothing else of d_seek is written: no max_bits word, no sub[] rows.
+ * With sym_base = bit_base = 0 and stream_nsym = n / 2 the table is the first
+ * hz_seek_bytes(n / 2) bytes of the index hz_pack writes.
+ * Stream-ordered and capturable like hz_pack. HZ_EINVAL at the call: what hz_pack
+ * rejects, a null d_seek, sym_base not a multiple of 2048, sym_base + n / 2 >
+ * stream_nsym, a call that is neither whole blocks nor the stream's last.
+ * n / 2 == 0: HZ_OK, nothing written. */
+int hz_pack_seek(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t start_bit, uint32_t lead,
+                 uint8_t *d_out, uint64_t out_cap, void *d_ranges /* nullable */,
+                 uint64_t sym_base, uint64_t bit_base, uint64_t stream_nsym, uint64_t *d_seek);
+
 /* ---- one index-less stream over several devices ------------
  * The same decode in PARTS: every device (rank) decodes the payload bits
  * [part_begin, part_end) (counted after start_bit) of one stream, found by
@@ -458,6 +483,24 @@ int hz_archive_file(const char *path, int verbose);
  * byte-identical to the whole-buffer encoder. hz_archive_file uses it with
  * 256 MiB chunks. Replaces the whole-file buffers of Compressor.cu:343-367,585-601. */
 int hz_archive_stream(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose);
+/* hz_archive_stream / hz_archive_file that also return the file's seek table,
+ * from the writer (hz_pack_seek): the same output bytes, no pass over the
+ * finished file. Bits count from the file byte that holds the first payload bit
+ * (hz_header_info's payload_byte), as hz_seek_build_host and
+ * hz_extract_stream_seek count, so the tables are interchangeable. Every chunk
+ * packs into one device table (sym_base = the symbols packed, bit_base = 8 x the
+ * payload bytes handed to the writer), copied out once at the end; the chunk's
+ * end bit is read from the table, no per-chunk block index. chunk_bytes is
+ * rounded down to a multiple of 4096 (at least 4096) so every chunk is whole
+ * blocks; the output does not depend on it. hz_archive_file_seek writes
+ * <path>.compressed, honours HZ_ARCHIVE_CHUNK and keeps the input resident under
+ * hz_archive_file's condition (then: one hz_pack_seek over the whole input).
+ * *nsym receives the file's symbols (size / 2); seek_cap_bytes <
+ * hz_seek_bytes(*nsym): HZ_ECAP with *nsym set, before any device work and before
+ * the output file is created. seek may be NULL when the table is empty. */
+int hz_archive_stream_seek(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose,
+                           uint64_t *seek, uint64_t seek_cap_bytes, uint64_t *nsym);
+int hz_archive_file_seek(const char *path, int verbose, uint64_t *seek, uint64_t seek_cap_bytes, uint64_t *nsym);
 /* Streaming extract of in_path into out_path through a device window of
  * chunk_bytes of payload, bounded host and device memory: each round decodes
  * the codewords the window surely holds with hz_decode_indexless (no block
@@ -508,6 +551,11 @@ int hz_extract_file(const char *path, char *out_name, size_t out_name_cap, int v
 int hz_encode_host(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len);
 int hz_encoded_size(const uint8_t *in, uint64_t n, uint64_t *out_len);
 int hz_decode_host(const uint8_t *file, uint64_t len, uint8_t *out, uint64_t cap, uint64_t *out_n);
+/* hz_encode_host that also returns the image's seek table from the writer (the
+ * table hz_seek_build_host finds in the image): hz_seek_bytes(n / 2) bytes at
+ * seek; seek_cap_bytes below that: HZ_ECAP before any device work. */
+int hz_encode_host_seek(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len,
+                        uint64_t *seek, uint64_t seek_cap_bytes);
 
 /* Whole-buffer host forms of random access (device work inside). hz_seek_build_host:
  * the seek table of a .compressed image (reference-written files included) into
