@@ -17,6 +17,7 @@ HZ_RANGE_LEAD_BYTES = 32
 HZ_RANGE_TAIL_BYTES = 32
 HZ_RANGE_FULL_INDEX = 1
 HZ_RANGES_STATS_WORDS = 4
+HZ_POS_LIMIT = (1 << 64) - 1 - 0xFFFF  # every stream position a base-taking call reaches stays below it
 
 STATUS = {
     0: "HZ_OK", -1: "HZ_EINVAL", -2: "HZ_ENOMEM", -3: "HZ_EHIP", -4: "HZ_ETOOLONG",

@@ -404,6 +404,16 @@ static uint64_t clamp_reach(const hz_ctx* c, uint64_t payload_bytes, uint64_t st
     return nsym <= (UINT64_MAX - start_bit) / 64 && payload_bytes > reach ? reach : payload_bytes;
 }
 
+// A base-taking call's largest stream position, base_bits + 8 * bytes, computed without a wrap: it must
+// stay below HZ_POS_LIMIT (include/huffman_amd.h "Stream positions"), else the call is refused before
+// anything is launched.
+static bool far_pos_ok(uint64_t base_bits, uint64_t bytes) {
+    return bytes <= (HZ_POS_LIMIT - 1) / 8 && base_bits <= HZ_POS_LIMIT - 1 - 8 * bytes;
+}
+static bool far_byte_pos_ok(uint64_t base_bytes, uint64_t bytes) {
+    return base_bytes <= (HZ_POS_LIMIT - 1) / 8 && far_pos_ok(8 * base_bytes, bytes);
+}
+
 // hz_pack_seek's placement: the call packs symbols [sym_base, sym_base + n / 2) of a stream of stream_nsym
 // and writes their entries of the table at d_seek (addressed from entry 0), each counted bit_base
 // further than from byte 0 of d_out.
@@ -468,6 +478,7 @@ extern "C" int hz_pack_seek(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t
     if (sym_base % kBlockSyms || sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
     // whole blocks, or the stream's last call: every entry of the window is a block start of this call
     if (nsym % kBlockSyms && sym_base + nsym != stream_nsym) return HZ_EINVAL;
+    if (!far_pos_ok(bit_base, out_cap)) return HZ_EINVAL;  // no entry can wrap: a block ends within out_cap
     const bool plan = d_ranges && range_geom(nsym).bytes;
     if (plan && (((uintptr_t)d_ranges) & 15)) return HZ_EINVAL;
     const PackSeek sk{sym_base, bit_base, stream_nsym, d_seek};
@@ -536,6 +547,7 @@ extern "C" int hz_decode_range(hz_ctx* c, const uint8_t* d_payload, uint64_t pay
     if (!c || !d_payload || !d_seek || !d_out) return HZ_EINVAL;
     if ((flags & ~HZ_RANGE_FULL_INDEX) || (((uintptr_t)d_out) & 1)) return HZ_EINVAL;
     if (sym_begin > nsym || sym_count > nsym - sym_begin) return HZ_EINVAL;
+    if (!far_byte_pos_ok(payload_byte_base, payload_bytes)) return HZ_EINVAL;
     if (sym_count == 0) return HZ_OK;
     if (c->t.dec_mode < 0) return HZ_EINVAL;
     HZ_TRY(hipSetDevice(c->device));
@@ -554,6 +566,7 @@ extern "C" int hz_decode_ranges(hz_ctx* c, const uint8_t* d_payload, uint64_t pa
     if (!c || !d_payload || !d_seek || !d_ranges || !d_out) return HZ_EINVAL;
     if ((flags & ~HZ_RANGE_FULL_INDEX) || (((uintptr_t)d_out) & 1)) return HZ_EINVAL;
     if (c->t.dec_mode < 0) return HZ_EINVAL;
+    if (!far_byte_pos_ok(payload_byte_base, payload_bytes)) return HZ_EINVAL;
     if (nranges == 0) return HZ_OK;
     HZ_TRY(hipSetDevice(c->device));
     int rc = ensure_scratch(c, ranges_scratch_words(nranges));
@@ -651,6 +664,7 @@ extern "C" int hz_decode_indexless_seek(hz_ctx* c, const uint8_t* d_payload, uin
                                         uint64_t bit_base, uint64_t stream_nsym, uint64_t* d_seek) {
     if (!c || !d_seek || (((uintptr_t)d_out) & 15)) return HZ_EINVAL;
     if (sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
+    if (!far_pos_ok(bit_base, payload_bytes)) return HZ_EINVAL;  // no entry can wrap: a held codeword starts in the payload
     if (c->t.dec_mode < 0) return HZ_EINVAL;
     if (nsym == 0) return HZ_OK;
     if (!d_payload) return HZ_EINVAL;
@@ -684,7 +698,7 @@ extern "C" int hz_indexless_scan(hz_ctx* c, const uint8_t* d_payload, uint64_t p
                                  uint64_t entry_bit, uint64_t* d_summary) {
     if (!c || !d_payload || part_end <= part_begin || payload_bytes < 16) return HZ_EINVAL;
     if (c->t.dec_mode < 0) return HZ_EINVAL;
-    if (start_bit > UINT64_MAX - part_end || payload_bytes > (UINT64_MAX - payload_bit_base) / 8) return HZ_EINVAL;
+    if (start_bit > UINT64_MAX - part_end || !far_pos_ok(payload_bit_base, payload_bytes)) return HZ_EINVAL;
     // the view must hold the part, and the lead-in before it (the stream's bits from its start, when the
     // part begins less than HZ_INDEXLESS_LEAD_BITS into it)
     const uint64_t lead = part_begin < HZ_INDEXLESS_LEAD_BITS ? part_begin : HZ_INDEXLESS_LEAD_BITS;

@@ -67,6 +67,20 @@ typedef struct hz_header_info {
 
 typedef struct hz_ctx hz_ctx;
 
+/* Stream positions. Bit positions, seek entries and bases are u64 and may lie
+ * anywhere in a stream of any size: a base lets a small device buffer stand for
+ * a piece of a much larger stream. UINT64_MAX marks a position that does not
+ * exist (a codeword the payload does not hold), and the kernels add alignment
+ * offsets and margins of less than 2^16 bits to a position, so every position a
+ * call can reach stays below HZ_POS_LIMIT. A base-taking call whose largest
+ * position is HZ_POS_LIMIT or more, or does not fit 64 bits at all, returns
+ * HZ_EINVAL at the call with nothing launched:
+ *   hz_decode_range, hz_decode_ranges   8 * (payload_byte_base + payload_bytes)
+ *   hz_pack_seek                        bit_base + 8 * out_cap
+ *   hz_decode_indexless_seek            bit_base + 8 * payload_bytes
+ *   hz_indexless_scan                   payload_bit_base + 8 * payload_bytes */
+#define HZ_POS_LIMIT (UINT64_MAX - 0xFFFFu)
+
 const char *hz_strerror(int status);
 int hz_version(void);
 
@@ -268,7 +282,8 @@ int hz_seek_span(const uint64_t *seek, uint64_t nsym, uint64_t sym_begin, uint64
  * many blocks per tile with a full index, which needs no sub[] rows). Ends a pending
  * index-less part like every scratch user.
  * HZ_EINVAL at the call: null pointers, sym_begin + sym_count > nsym, an odd
- * d_out, unknown flags, no decode tables. sym_count 0: HZ_OK, nothing launched.
+ * d_out, unknown flags, no decode tables, 8 * (payload_byte_base + payload_bytes)
+ * not below HZ_POS_LIMIT. sym_count 0: HZ_OK, nothing launched.
  * Found on the device and reported by hz_ctx_sync, with nothing written for the
  * block concerned: HZ_EINVAL for a block whose bytes and margins are not inside
  * the slice; HZ_EFORMAT for a descending start[], for a block longer than its
@@ -301,8 +316,8 @@ int hz_decode_range(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_byte
  * pending index-less part like every scratch user, and the host waits only when
  * the scratch must grow. No other host synchronisation and no host copy.
  * HZ_EINVAL at the call: null pointers (d_stats may be null), unknown flags, an
- * odd d_out, no decode tables. nranges 0: HZ_OK, nothing launched (d_stats is
- * left as it was).
+ * odd d_out, no decode tables, 8 * (payload_byte_base + payload_bytes) not below
+ * HZ_POS_LIMIT. nranges 0: HZ_OK, nothing launched (d_stats is left as it was).
  * Found on the device and reported by hz_ctx_sync: HZ_EINVAL for a range with
  * sym_begin + sym_count > nsym, an odd out_byte or out_byte + 2 * sym_count >
  * out_bytes (nothing is written for that range) and for a block whose bytes and
@@ -386,8 +401,9 @@ int hz_decode_indexless(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_
  *
  * Stream-ordered and capturable; the host waits only when the scratch grows.
  * HZ_EINVAL at the call: a null d_seek, sym_base + nsym > stream_nsym, no decode
- * tables, a non-null d_out that is not 16-byte aligned, no pending part. nsym 0:
- * HZ_OK, nothing written. An invalid code reports HZ_EFORMAT at hz_ctx_sync. */
+ * tables, a non-null d_out that is not 16-byte aligned, no pending part,
+ * bit_base + 8 * payload_bytes not below HZ_POS_LIMIT. nsym 0: HZ_OK, nothing
+ * written. An invalid code reports HZ_EFORMAT at hz_ctx_sync. */
 int hz_seek_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
                   uint64_t nsym, uint64_t *d_seek);
 int hz_decode_indexless_seek(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
@@ -414,7 +430,8 @@ int hz_indexless_seek(hz_ctx *ctx, uint64_t sym_base, uint64_t nsym, uint64_t st
  * hz_seek_bytes(n / 2) bytes of the index hz_pack writes.
  * Stream-ordered and capturable like hz_pack. HZ_EINVAL at the call: what hz_pack
  * rejects, a null d_seek, sym_base not a multiple of 2048, sym_base + n / 2 >
- * stream_nsym, a call that is neither whole blocks nor the stream's last.
+ * stream_nsym, a call that is neither whole blocks nor the stream's last,
+ * bit_base + 8 * out_cap not below HZ_POS_LIMIT.
  * n / 2 == 0: HZ_OK, nothing written. */
 int hz_pack_seek(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t start_bit, uint32_t lead,
                  uint8_t *d_out, uint64_t out_cap, void *d_ranges /* nullable */,
@@ -436,10 +453,11 @@ int hz_pack_seek(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t start_bi
  *       [payload_bit_base, payload_bit_base + 8 * payload_bytes) -- a rank may
  *       pass only its slice (payload_bit_base a multiple of 8). The slice must
  *       hold the part and the HZ_INDEXLESS_LEAD_BITS before it (or the stream
- *       from its start), else HZ_EINVAL; the part's last codeword may run up to
- *       max_len bits past part_end (missing bits read as zeros: keep them in
- *       the slice). nsym: the stream's symbols (sizes the part's record capacity
- *       from its mean bits per codeword; 0 = unknown: the codebook's estimate).
+ *       from its start) and end below HZ_POS_LIMIT, else HZ_EINVAL; the part's
+ *       last codeword may run up to max_len bits past part_end (missing bits
+ *       read as zeros: keep them in the slice). nsym: the stream's symbols
+ *       (sizes the part's record capacity from its mean bits per codeword;
+ *       0 = unknown: the codebook's estimate).
  *   hz_indexless_refix : the part again from its true entry (the previous
  *       part's exit, when it differs from the walked entry); d_summary updated.
  *   hz_indexless_decode : the part's codewords into d_out (2 bytes each, from

@@ -118,3 +118,82 @@ def test_python_wrapper(built_lib, romeo):
     assert huffman_amd.seek_span(seek, nsym, 0, nsym) == (0, pay + 32)
     with pytest.raises(huffman_amd.HZError):
         huffman_amd.seek_span(seek, nsym, 1, nsym)
+
+
+# ---- far tables: positions past 2^32 bits, bytes and symbols -----------------------------------------
+FAR_BITS = [1 << 32, 1 << 35, 1 << 37, 1 << 48]          # u32 bit position, byte offset, word index, any file size
+FAR_BLOCKS = [0, 1 << 20, 1 << 21, (1 << 22) + 1]        # first block: output byte 2 sym = 2^32, sym = 2^32, past both
+FAR_NB = 9
+
+
+def _far_table(T, b0):
+    """A host table of a stream whose blocks [b0, b0 + 9) (the last one ragged) are the only ones written:
+    synthetic block sizes of 9 000 to 40 000 bits, placed so that bit T falls inside block b0 + 4."""
+    rng = np.random.default_rng(T % 1000003 + b0)
+    sizes = [int(v) for v in rng.integers(9000, 40000, FAR_NB)]
+    near = [0]
+    for v in sizes:
+        near.append(near[-1] + v)
+    shift = T - (near[4] + near[5]) // 2
+    nsym = BLK * b0 + (FAR_NB - 1) * BLK + 5
+    seek = np.zeros(b0 + FAR_NB + 1, dtype=np.uint64)    # (untouched pages of the zeros are never mapped)
+    starts = [shift + v for v in near]
+    seek[b0:] = np.array(starts, dtype=np.uint64)
+    assert starts[4] < T < starts[5]
+    return nsym, seek, starts
+
+
+def _rule(starts, k0, k1):
+    """include/huffman_amd.h in plain integers: 32 bytes before the first block's start byte, rounded down
+    to 16 and never below 0; 32 bytes after the last block's end byte."""
+    first = starts[k0] // 8
+    last = -(-starts[k1 + 1] // 8)
+    begin = ((first - 32) // 16) * 16 if first > 32 else 0
+    return begin, last + 32
+
+
+@pytest.mark.parametrize("b0", FAR_BLOCKS, ids=lambda v: "b0_%d" % v)
+@pytest.mark.parametrize("T", FAR_BITS, ids=lambda v: "T2p%d" % (v.bit_length() - 1))
+def test_span_on_far_tables(built_lib, T, b0):
+    nsym, seek, starts = _far_table(T, b0)
+    s0 = BLK * b0
+    cases = [(0, nsym - s0), (0, 1), (nsym - s0 - 1, 1), (4 * BLK, 1), (4 * BLK, BLK), (3 * BLK + 7, 2 * BLK),
+             (4 * BLK - 1, 2), (5 * BLK, 3 * BLK + 5), (8 * BLK, 5)]
+    for begin, count in cases:
+        k0, k1 = begin // BLK, (begin + count - 1) // BLK
+        rc, bb, be = _span(built_lib, seek, nsym, s0 + begin, count)
+        assert rc == 0, (begin, count)
+        assert (bb, be) == _rule(starts, k0, k1), (begin, count, bb, be)
+    # the blocks around T hold positions below and above it
+    _, bb, be = _span(built_lib, seek, nsym, s0 + 4 * BLK, 1)
+    assert 8 * bb < T < 8 * be
+    assert _span(built_lib, seek, nsym, s0 + 7, 0) == (0, 0, 0)
+    assert _span(built_lib, seek, nsym, nsym, 1)[0] == HZ_EINVAL
+
+
+def test_span_straddles_byte_2p32_and_symbol_2p32(built_lib):
+    """One range whose blocks lie on both sides of payload byte 2^32 (bit 2^35), in a stream whose range
+    begins at or past symbol 2^32."""
+    T, b0 = 1 << 35, 1 << 21
+    nsym, seek, starts = _far_table(T, b0)
+    sym_begin = BLK * b0 + 3 * BLK + 100
+    assert sym_begin >= 1 << 32
+    rc, bb, be = _span(built_lib, seek, nsym, sym_begin, 3 * BLK)
+    assert rc == 0 and bb < (1 << 32) < be
+    assert (bb, be) == _rule(starts, 3, 6)
+    assert starts[3] // 8 < (1 << 32) < starts[7] // 8
+    # a descending far table is refused
+    bad = seek.copy()
+    bad[b0 + 7] = bad[b0 + 3] - np.uint64(16)   # its end byte lies below the first block's start byte
+    assert _span(built_lib, bad, nsym, sym_begin, 3 * BLK)[0] == HZ_EINVAL
+
+
+def test_position_limit_exported(built_lib):
+    """The binding's HZ_POS_LIMIT is the header's: UINT64_MAX - 0xFFFF, written there as that expression."""
+    import re
+    from huffman_amd import _lib
+    with open(os.path.join(ROOT, "include", "huffman_amd.h")) as f:
+        text = f.read()
+    m = re.search(r"#define HZ_POS_LIMIT \(UINT64_MAX - (0x[0-9A-Fa-f]+)u\)", text)
+    assert m, "HZ_POS_LIMIT is not defined as UINT64_MAX - <hex>u"
+    assert _lib.HZ_POS_LIMIT == (1 << 64) - 1 - int(m.group(1), 16)
