@@ -70,6 +70,16 @@ class StreamTiming(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class Piece(ctypes.Structure):
+    """hz_piece: a contiguous run of a stream's payload in a gathered buffer, and its seek entries."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("stream_byte", "bytes", "buf_byte", "first_block", "seek_index", "nblocks")]
+
+
+class PieceRange(ctypes.Structure):
+    """hz_piece_range: hz_range plus the piece that holds the range's span."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("sym_begin", "sym_count", "out_byte", "piece")]
+
+
 # (name, restype, argtypes): exactly the entry points include/huffman_amd.h declares.
 PROTOTYPES = [
     ("hz_strerror", ctypes.c_char_p, [_I]),
@@ -108,6 +118,9 @@ PROTOTYPES = [
     ("hz_seek_span", _I, [_P, _U64, _U64, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hz_decode_range", _I, [_P, _P, _U64, _U64, _P, _U64, _U64, _U64, _P, _U32]),
     ("hz_decode_ranges", _I, [_P, _P, _U64, _U64, _P, _U64, _P, _U32, _P, _U64, _P, _U32]),
+    ("hz_decode_ranges_pieces", _I, [_P, _P, _U64, _P, _U64, _P, _U32, _U64, _P, _U32, _P, _U64, _P, _U32]),
+    ("hz_seek_pieces", _I, [_P, _U64, _U64, _P, _U32, _P, ctypes.POINTER(_U32), _P, ctypes.POINTER(_U64),
+                            ctypes.POINTER(_U64)]),
     ("hz_index_expand", _I, [_P, _P, _U64, _P, _U64, _P]),
     ("hz_decode_indexless", _I, [_P, _P, _U64, _U64, _U64, _P, _P]),
     ("hz_indexless_scan", _I, [_P, _P, _U64, _U64, _U64, _U64, _U64, _U64, _U64, _P]),
@@ -134,6 +147,8 @@ PROTOTYPES = [
     ("hz_seek_build_host", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
     ("hz_decode_range_host", _I, [_P, _U64, _P, _U64, _U64, _P]),
     ("hz_decode_ranges_host", _I, [_P, _U64, _P, _P, _P, _U32, _P]),
+    ("hz_decode_ranges_host_pieces", _I, [_P, _U64, _P, _P, _P, _U32, _P]),
+    ("hz_decode_ranges_file", _I, [ctypes.c_char_p, _P, _P, _P, _U32, _P]),
 ]
 
 _lib = None

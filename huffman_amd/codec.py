@@ -206,6 +206,28 @@ def seek_span(seek_host, nsym, sym_begin, sym_count):
     return b.value, e.value
 
 
+PIECE_DTYPE = np.dtype([(n, np.uint64) for n in ("stream_byte", "bytes", "buf_byte", "first_block", "seek_index", "nblocks")])
+PIECE_RANGE_DTYPE = np.dtype([(n, np.uint64) for n in ("sym_begin", "sym_count", "out_byte", "piece")])
+
+
+def seek_pieces(seek_host, nsym, payload_bytes, ranges):
+    """The plan of a gathered buffer (hz_seek_pieces): host arithmetic. ranges: [(sym_begin, sym_count,
+    out_byte), ...]. Returns (pieces, piece_ranges, buf_bytes, seek_words): numpy structured arrays of
+    PIECE_DTYPE (one per piece) and PIECE_RANGE_DTYPE (one per range), and the two totals."""
+    seek = np.ascontiguousarray(seek_host, dtype=np.uint64)
+    if seek.size * 8 < seek_bytes(nsym):
+        raise ValueError("seek table shorter than seek_bytes(nsym)")
+    rg = np.ascontiguousarray(np.array([[int(v) for v in r] for r in ranges], dtype=np.uint64).reshape(-1, 3))
+    n = rg.shape[0]
+    pieces = np.zeros(max(n, 1), dtype=PIECE_DTYPE)
+    out = np.zeros(max(n, 1), dtype=PIECE_RANGE_DTYPE)
+    np_, bb, sw = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(load().hz_seek_pieces(seek.ctypes.data_as(ctypes.c_void_p), nsym, payload_bytes, rg.ctypes.data_as(ctypes.c_void_p),
+                                n, pieces.ctypes.data_as(ctypes.c_void_p), ctypes.byref(np_),
+                                out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(bb), ctypes.byref(sw)), "hz_seek_pieces")
+    return pieces[:np_.value], out[:n], bb.value, sw.value
+
+
 def build_seek(blob):
     """.compressed image -> its seek table (uint64 start[nblocks + 1]; bits count from the file byte
     that holds the first payload bit). Works on files the reference wrote."""
@@ -269,20 +291,44 @@ def decode_range_file(path, seek, offset, length):
     return out[:length].tobytes()
 
 
-def decode_ranges(blob, seek, ranges):
+def _byte_ranges(ranges):
+    offs = np.array([int(o) for o, _ in ranges], dtype=np.uint64)
+    cnts = np.array([int(c) for _, c in ranges], dtype=np.uint64)
+    return offs, cnts, np.empty(max(int(cnts.sum()), 1), dtype=np.uint8)
+
+
+def _split(out, cnts):
+    ends = np.cumsum(cnts).astype(np.int64)
+    return [out[int(e) - int(c):int(e)].tobytes() for e, c in zip(ends, cnts)]
+
+
+def decode_ranges(blob, seek, ranges, pieces=False):
     """[(offset, length), ...] byte ranges of the original from a .compressed image and its seek table,
-    decoded in one device call (hz_decode_ranges_host): a list of bytes, in the ranges' order."""
+    decoded in one device call: a list of bytes, in the ranges' order. By default one payload slice that
+    covers every range goes to the device (hz_decode_ranges_host); pieces=True sends only the bytes and
+    table words each range needs, gathered (hz_decode_ranges_host_pieces)."""
     lib = load()
     arr, p = _buf(blob)
     sk = np.ascontiguousarray(seek, dtype=np.uint64)
-    offs = np.array([int(o) for o, _ in ranges], dtype=np.uint64)
-    cnts = np.array([int(c) for _, c in ranges], dtype=np.uint64)
-    out = np.empty(max(int(cnts.sum()), 1), dtype=np.uint8)
-    check(lib.hz_decode_ranges_host(p, arr.size, sk.ctypes.data_as(ctypes.c_void_p), offs.ctypes.data_as(ctypes.c_void_p),
-                                    cnts.ctypes.data_as(ctypes.c_void_p), offs.size,
-                                    out.ctypes.data_as(ctypes.c_void_p)), "hz_decode_ranges_host")
-    ends = np.cumsum(cnts).astype(np.int64)
-    return [out[int(e) - int(c):int(e)].tobytes() for e, c in zip(ends, cnts)]
+    offs, cnts, out = _byte_ranges(ranges)
+    fn, name = (lib.hz_decode_ranges_host_pieces, "hz_decode_ranges_host_pieces") if pieces else \
+        (lib.hz_decode_ranges_host, "hz_decode_ranges_host")
+    check(fn(p, arr.size, sk.ctypes.data_as(ctypes.c_void_p), offs.ctypes.data_as(ctypes.c_void_p),
+             cnts.ctypes.data_as(ctypes.c_void_p), offs.size, out.ctypes.data_as(ctypes.c_void_p)), name)
+    return _split(out, cnts)
+
+
+def decode_ranges_file(path, seek, ranges):
+    """[(offset, length), ...] byte ranges of the original from a .compressed file on disk and its seek
+    table, in one device call from gathered pieces: the header and each piece's bytes are read, nothing
+    else (hz_decode_ranges_file). A list of bytes, in the ranges' order."""
+    lib = load()
+    sk = np.ascontiguousarray(seek, dtype=np.uint64)
+    offs, cnts, out = _byte_ranges(ranges)
+    check(lib.hz_decode_ranges_file(os.fsencode(path), sk.ctypes.data_as(ctypes.c_void_p),
+                                    offs.ctypes.data_as(ctypes.c_void_p), cnts.ctypes.data_as(ctypes.c_void_p), offs.size,
+                                    out.ctypes.data_as(ctypes.c_void_p)), "hz_decode_ranges_file")
+    return _split(out, cnts)
 
 
 class Device:
@@ -394,6 +440,15 @@ class Device:
         check(self.lib.hz_decode_ranges(self.h, d_payload, payload_bytes, payload_byte_base, d_seek, nsym, d_ranges,
                                         nranges, d_out, out_bytes, d_stats,
                                         _lib.HZ_RANGE_FULL_INDEX if full_index else 0), "hz_decode_ranges")
+
+    def decode_ranges_pieces(self, d_buf, buf_bytes, d_seek, seek_words, d_pieces, npieces, nsym, d_ranges, nranges,
+                             d_out, out_bytes, d_stats=None, flags=0):
+        """A batch of ranges from gathered pieces (hz_decode_ranges_pieces). d_pieces: npieces x 6 u64,
+        d_ranges: nranges x (sym_begin, sym_count, out_byte, piece) u64, d_seek: the compact table, all on
+        the device; d_stats: 4 u64 on the device, or None."""
+        check(self.lib.hz_decode_ranges_pieces(self.h, d_buf, buf_bytes, d_seek, seek_words, d_pieces, npieces, nsym,
+                                               d_ranges, nranges, d_out, out_bytes, d_stats, flags),
+              "hz_decode_ranges_pieces")
 
     def index_expand(self, d_payload, payload_bytes, d_seek, nsym, d_index):
         """Seek table -> the complete block index (d_seek may be d_index)."""

@@ -278,6 +278,11 @@ struct BitReader {
     uint64_t abase;     // word index of `ahead`
 };
 
+// The reader's chunk load. br_init / br_word / br_next call it unqualified on their argument type A, so
+// a type derived from DecArgs in namespace hz may overload it (a non-template beats this template; it is
+// found by argument-dependent lookup where the readers are instantiated). hz_ranges.hip does, for
+// PieceDecArgs, whose view also ends at its lower end: keep that type and its overload in namespace hz
+// and the overload's parameter the derived type itself, or the readers fall back to this one silently.
 template <typename A>
 HZ_DEV uint4 ld_chunk(const A& a, uint64_t w) {  // w % 4 == 0
     if (w + 4 <= a.nwords) return *reinterpret_cast<const uint4*>(a.words + w);
@@ -317,9 +322,10 @@ HZ_DEV void br_init(BitReader& r, const A& a, uint64_t p) {
     r.nxt = br_word(r, a);
 }
 
-// Length (and symbol) of the codeword at the reader, then advance past it.
-template <int MODE>
-HZ_DEV uint32_t br_next(BitReader& r, const DecArgs& a, const uint32_t* lds, uint32_t& sym) {
+// Length (and symbol) of the codeword at the reader, then advance past it. A: DecArgs or a type derived
+// from it (the reader's loads are ld_chunk's of that type).
+template <int MODE, typename A>
+HZ_DEV uint32_t br_next(BitReader& r, const A& a, const uint32_t* lds, uint32_t& sym) {
     if (r.nb <= 32) {
         r.buf |= (uint64_t)r.nxt << (32 - r.nb);
         r.nb += 32;

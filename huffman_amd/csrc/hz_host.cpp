@@ -523,23 +523,7 @@ extern "C" int hz_index_build(hz_ctx* c, const uint8_t* d_payload, uint64_t payl
 // ---- random access: seek table and range decode ----------------------------
 extern "C" uint64_t hz_seek_bytes(uint64_t nsym) { return nsym ? 8 * (index_blocks(nsym) + 1) : 0; }
 
-extern "C" int hz_seek_span(const uint64_t* seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
-                            uint64_t* byte_begin, uint64_t* byte_end) {
-    if (!byte_begin || !byte_end) return HZ_EINVAL;
-    if (sym_begin > nsym || sym_count > nsym - sym_begin) return HZ_EINVAL;
-    *byte_begin = *byte_end = 0;
-    if (sym_count == 0) return HZ_OK;
-    if (!seek) return HZ_EINVAL;
-    const uint64_t b0 = sym_begin / kBlockSyms, b1 = (sym_begin + sym_count - 1) / kBlockSyms;
-    const uint64_t first = seek[b0] / 8, last = seek[b1 + 1] / 8 + (seek[b1 + 1] % 8 ? 1 : 0);
-    if (last < first) return HZ_EINVAL;
-    // the staging window of a block starts 16 bytes below the 16-byte chunk of its first bit
-    // (dec_stage_prefetch / dec_stage_commit; the walk's reader starts at that chunk, br_init) and
-    // ends with the chunk two words past its last bit; the reader runs one chunk ahead
-    *byte_begin = first > kRangeLeadBytes ? (first - kRangeLeadBytes) & ~15ull : 0;
-    *byte_end = last + kRangeTailBytes;
-    return HZ_OK;
-}
+// (hz_seek_span and hz_seek_pieces, host arithmetic on a host table: hz_seek_plan.cpp)
 
 extern "C" int hz_decode_range(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t payload_byte_base,
                                const uint64_t* d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
@@ -576,6 +560,29 @@ extern "C" int hz_decode_ranges(hz_ctx* c, const uint8_t* d_payload, uint64_t pa
                                     reinterpret_cast<const unsigned long long*>(d_seek), nsym, d_ranges, nranges, d_out,
                                     out_bytes, reinterpret_cast<unsigned long long*>(d_stats),
                                     (flags & HZ_RANGE_FULL_INDEX) != 0, c->d_desc, c->d_err, c->ncu, c->stream);
+    });
+}
+
+extern "C" int hz_decode_ranges_pieces(hz_ctx* c, const uint8_t* d_buf, uint64_t buf_bytes, const uint64_t* d_seek,
+                                       uint64_t seek_words, const hz_piece* d_pieces, uint32_t npieces, uint64_t nsym,
+                                       const hz_piece_range* d_ranges, uint32_t nranges, uint8_t* d_out,
+                                       uint64_t out_bytes, uint64_t* d_stats, uint32_t flags) {
+    if (!c || !d_buf || !d_seek || !d_pieces || !d_ranges || !d_out) return HZ_EINVAL;
+    if (flags || (((uintptr_t)d_out) & 1)) return HZ_EINVAL;
+    // a piece's first word is the one that holds its first byte: with d_buf off the 4-byte grid that
+    // word would begin below the buffer
+    if (((uintptr_t)d_buf) & 3) return HZ_EINVAL;
+    if (c->t.dec_mode < 0) return HZ_EINVAL;
+    if (!far_byte_pos_ok(0, buf_bytes)) return HZ_EINVAL;
+    if (nranges == 0) return HZ_OK;
+    HZ_TRY(hipSetDevice(c->device));
+    int rc = ensure_scratch(c, ranges_scratch_words(nranges));
+    if (rc) return rc;
+    return timed_stage(c, HZ_STAGE_DECODE, "launch_decode_ranges_pieces", [&] {
+        return launch_decode_ranges_pieces(c->t, d_buf, buf_bytes, reinterpret_cast<const unsigned long long*>(d_seek),
+                                           seek_words, d_pieces, npieces, nsym, d_ranges, nranges, d_out, out_bytes,
+                                           reinterpret_cast<unsigned long long*>(d_stats), c->d_desc, c->d_err, c->ncu,
+                                           c->stream);
     });
 }
 

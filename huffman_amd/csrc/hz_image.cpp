@@ -270,6 +270,37 @@ int decode_range_image(const uint8_t* f, uint64_t len, const uint64_t* seek, uin
     return rc ? rc : decode_range_opened(im, seek, offset, count, out);
 }
 
+// The covering symbol ranges of byte ranges [offsets[i], offsets[i] + counts[i]) of the original, their
+// symbols laid end to end in a temporary of *tmp_bytes; *total: the bytes asked for.
+int byte_ranges(const OpenedImage& im, const uint64_t* offsets, const uint64_t* counts, uint32_t nranges,
+                std::vector<hz_range>& rg, uint64_t* tmp_bytes, uint64_t* total) {
+    rg.resize(nranges);
+    *tmp_bytes = *total = 0;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (offsets[i] > im.info.n || counts[i] > im.info.n - offsets[i]) return HZ_EINVAL;
+        const uint64_t s0 = offsets[i] / 2, s1 = std::min((offsets[i] + counts[i] + 1) / 2, im.nsym);  // covering symbols
+        rg[i].sym_begin = s0;
+        rg[i].sym_count = counts[i] && s1 > s0 ? s1 - s0 : 0;
+        rg[i].out_byte = *tmp_bytes;
+        *tmp_bytes += 2 * rg[i].sym_count;
+        *total += counts[i];
+    }
+    return HZ_OK;
+}
+
+// The decoded temporary to the caller: odd offsets clipped, the odd last byte from the header, list order.
+void give_byte_ranges(const OpenedImage& im, const std::vector<hz_range>& rg, const std::vector<uint8_t>& tmp,
+                      const uint64_t* offsets, const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    uint8_t* o = out;
+    for (uint32_t i = 0; i < nranges; ++i) {
+        if (!counts[i]) continue;
+        const uint64_t skip = offsets[i] - 2 * rg[i].sym_begin, have = 2 * rg[i].sym_count;
+        if (have > skip) memcpy(o, tmp.data() + rg[i].out_byte + skip, std::min<uint64_t>(counts[i], have - skip));
+        if (im.info.is_odd && offsets[i] + counts[i] == im.info.n) o[counts[i] - 1] = (uint8_t)im.info.last_byte;
+        o += counts[i];
+    }
+}
+
 // Byte ranges [offsets[i], offsets[i] + counts[i]) of the original, concatenated in `out`: one
 // hz_decode_ranges call over one payload slice (the smallest byte_begin to the largest byte_end).
 int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
@@ -279,24 +310,18 @@ int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, co
     if (rc) return rc;
     if (nranges == 0) return HZ_OK;
     if (!offsets || !counts) return HZ_EINVAL;
-    std::vector<hz_range> rg(nranges);
-    uint64_t tmp_bytes = 0, total = 0, bb = UINT64_MAX, be = 0, b0 = UINT64_MAX, b1 = 0;
+    std::vector<hz_range> rg;
+    uint64_t tmp_bytes, total, bb = UINT64_MAX, be = 0, b0 = UINT64_MAX, b1 = 0;
+    if ((rc = byte_ranges(im, offsets, counts, nranges, rg, &tmp_bytes, &total))) return rc;
     for (uint32_t i = 0; i < nranges; ++i) {
-        if (offsets[i] > im.info.n || counts[i] > im.info.n - offsets[i]) return HZ_EINVAL;
-        const uint64_t s0 = offsets[i] / 2, s1 = std::min((offsets[i] + counts[i] + 1) / 2, im.nsym);  // covering symbols
-        rg[i].sym_begin = s0;
-        rg[i].sym_count = counts[i] && s1 > s0 ? s1 - s0 : 0;
-        rg[i].out_byte = tmp_bytes;
-        tmp_bytes += 2 * rg[i].sym_count;
-        total += counts[i];
         if (rg[i].sym_count) {
             if (!seek) return HZ_EINVAL;
             uint64_t rb, re;
-            if ((rc = hz_seek_span(seek, im.nsym, s0, rg[i].sym_count, &rb, &re))) return rc;
+            if ((rc = hz_seek_span(seek, im.nsym, rg[i].sym_begin, rg[i].sym_count, &rb, &re))) return rc;
             bb = std::min(bb, rb);
             be = std::max(be, re);
-            b0 = std::min(b0, s0 / kBlockSyms);
-            b1 = std::max(b1, (s1 - 1) / kBlockSyms);
+            b0 = std::min(b0, rg[i].sym_begin / kBlockSyms);
+            b1 = std::max(b1, (rg[i].sym_begin + rg[i].sym_count - 1) / kBlockSyms);
         }
     }
     if (total && !out) return HZ_EINVAL;
@@ -321,14 +346,62 @@ int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, co
         HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
         if ((rc = hz_ctx_sync(c))) return rc;
     }
-    uint8_t* o = out;
-    for (uint32_t i = 0; i < nranges; ++i) {
-        if (!counts[i]) continue;
-        const uint64_t skip = offsets[i] - 2 * rg[i].sym_begin, have = 2 * rg[i].sym_count;
-        if (have > skip) memcpy(o, tmp.data() + rg[i].out_byte + skip, std::min<uint64_t>(counts[i], have - skip));
-        if (im.info.is_odd && offsets[i] + counts[i] == im.info.n) o[counts[i] - 1] = (uint8_t)im.info.last_byte;
-        o += counts[i];
+    give_byte_ranges(im, rg, tmp, offsets, counts, nranges, out);
+    return HZ_OK;
+}
+
+// The same bytes from gathered pieces, of an image in memory or a file on disk: hz_seek_pieces' plan,
+// one zeroed host buffer with each piece copied (or read) into its place, the compact table, one copy
+// each of buffer, table, pieces and ranges to the device, one hz_decode_ranges_pieces, one copy back,
+// one sync. Nothing of the payload outside the pieces is touched.
+int decode_ranges_pieces_opened(const OpenedImage& im, const uint64_t* seek, const uint64_t* offsets,
+                                const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    int rc;
+    if (nranges == 0) return HZ_OK;
+    if (!offsets || !counts) return HZ_EINVAL;
+    std::vector<hz_range> rg;
+    uint64_t tmp_bytes, total;
+    if ((rc = byte_ranges(im, offsets, counts, nranges, rg, &tmp_bytes, &total))) return rc;
+    if (tmp_bytes && !seek) return HZ_EINVAL;
+    if (total && !out) return HZ_EINVAL;
+    std::vector<uint8_t> tmp(tmp_bytes);
+    if (tmp_bytes) {
+        std::vector<hz_piece> pieces(nranges);
+        std::vector<hz_piece_range> prg(nranges);
+        uint32_t np;
+        uint64_t buf_bytes, seek_words;
+        if ((rc = hz_seek_pieces(seek, im.nsym, im.pay, rg.data(), nranges, pieces.data(), &np, prg.data(), &buf_bytes,
+                                 &seek_words)))
+            return rc;
+        std::vector<uint8_t> buf(buf_bytes, 0);
+        std::vector<uint64_t> words(seek_words);
+        for (uint32_t k = 0; k < np; ++k) {
+            const hz_piece& p = pieces[k];
+            if (im.f) memcpy(buf.data() + p.buf_byte, im.f + im.info.payload_byte + p.stream_byte, p.bytes);
+            else if ((rc = im.read_at(buf.data() + p.buf_byte, p.bytes, im.info.payload_byte + p.stream_byte))) return rc;
+            std::copy(seek + p.first_block, seek + p.first_block + p.nblocks + 1, words.begin() + p.seek_index);
+        }
+        hz_ctx* c;
+        if ((rc = default_ctx(&c))) return rc;
+        HZ_TRY(hipSetDevice(c->device));
+        if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
+        DevBuf dbuf, dseek, dpc, drg, dout;
+        const uint64_t pc_bytes = sizeof(hz_piece) * (uint64_t)np, rg_bytes = sizeof(hz_piece_range) * (uint64_t)nranges;
+        if ((rc = dbuf.alloc(buf_bytes)) || (rc = dseek.alloc(8 * seek_words)) || (rc = dpc.alloc(pc_bytes)) ||
+            (rc = drg.alloc(rg_bytes)) || (rc = dout.alloc(tmp_bytes)))
+            return rc;
+        HZ_TRY(hipMemcpyAsync(dbuf.p, buf.data(), buf_bytes, hipMemcpyHostToDevice, c->stream));
+        HZ_TRY(hipMemcpyAsync(dseek.p, words.data(), 8 * seek_words, hipMemcpyHostToDevice, c->stream));
+        HZ_TRY(hipMemcpyAsync(dpc.p, pieces.data(), pc_bytes, hipMemcpyHostToDevice, c->stream));
+        HZ_TRY(hipMemcpyAsync(drg.p, prg.data(), rg_bytes, hipMemcpyHostToDevice, c->stream));
+        if ((rc = hz_decode_ranges_pieces(c, (const uint8_t*)dbuf.p, buf_bytes, (const uint64_t*)dseek.p, seek_words,
+                                          (const hz_piece*)dpc.p, np, im.nsym, (const hz_piece_range*)drg.p, nranges,
+                                          (uint8_t*)dout.p, tmp_bytes, nullptr, 0)))
+            return rc;
+        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = hz_ctx_sync(c))) return rc;  // the host buffers of the four copies live until here
     }
+    give_byte_ranges(im, rg, tmp, offsets, counts, nranges, out);
     return HZ_OK;
 }
 
@@ -398,6 +471,26 @@ extern "C" int hz_decode_ranges_host(const uint8_t* file, uint64_t len, const ui
                                      const uint64_t* counts, uint32_t nranges, uint8_t* out) {
     if (!file) return HZ_EINVAL;
     return guarded([&] { return decode_ranges_image(file, len, seek, offsets, counts, nranges, out); });
+}
+
+extern "C" int hz_decode_ranges_host_pieces(const uint8_t* file, uint64_t len, const uint64_t* seek, const uint64_t* offsets,
+                                            const uint64_t* counts, uint32_t nranges, uint8_t* out) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open(file, len);
+        return rc ? rc : decode_ranges_pieces_opened(im, seek, offsets, counts, nranges, out);
+    });
+}
+
+extern "C" int hz_decode_ranges_file(const char* path, const uint64_t* seek, const uint64_t* offsets, const uint64_t* counts,
+                                     uint32_t nranges, uint8_t* out) {
+    if (!path) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open_file(path);
+        return rc ? rc : decode_ranges_pieces_opened(im, seek, offsets, counts, nranges, out);
+    });
 }
 
 extern "C" int hz_decode_range_file(const char* path, const uint64_t* seek, uint64_t offset, uint64_t count, uint8_t* out) {

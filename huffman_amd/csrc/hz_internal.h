@@ -355,6 +355,13 @@ hipError_t launch_decode_ranges(const Tables& t, const uint8_t* d_payload, uint6
                                 uint32_t nranges, uint8_t* d_out, uint64_t out_bytes, unsigned long long* d_stats,
                                 bool full_index, unsigned long long* d_scratch, uint32_t* d_err, int ncu,
                                 hipStream_t s);
+// The same from gathered pieces (DESIGN.md "Gathered pieces"): d_pieces and d_ranges are device memory,
+// d_seek the compact table; every job builds its piece's view on the device. Same scratch.
+hipError_t launch_decode_ranges_pieces(const Tables& t, const uint8_t* d_buf, uint64_t buf_bytes,
+                                       const unsigned long long* d_seek, uint64_t seek_words, const hz_piece* d_pieces,
+                                       uint32_t npieces, uint64_t nsym, const hz_piece_range* d_ranges, uint32_t nranges,
+                                       uint8_t* d_out, uint64_t out_bytes, unsigned long long* d_stats,
+                                       unsigned long long* d_scratch, uint32_t* d_err, int ncu, hipStream_t s);
 // ---- hz_index.hip -----------------------------------------------------------
 hipError_t launch_index_build(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes,
                               uint64_t start_bit, uint64_t nsym, unsigned long long* d_index,

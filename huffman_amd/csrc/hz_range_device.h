@@ -1,5 +1,5 @@
 // hz_range_device.h -- what the two random-access units share (hz_decode.hip: hz_decode_range and
-// hz_index_expand; hz_ranges.hip: hz_decode_ranges): the moved payload view, the seek pass's arguments,
+// hz_index_expand; hz_ranges.hip: hz_decode_ranges, hz_decode_ranges_pieces): the moved payload view, the seek pass's arguments,
 // the per-block checks and the FIXED16 step. Plain structs, force-inlined device
 // functions and one host helper; no kernel (DESIGN.md "Source layout": a new caller of shared
 // force-inlined code gets a unit of its own).
@@ -49,26 +49,49 @@ HZ_DEV void fixed16_step(const uint16_t* t16, const uint32_t (&ww)[5], uint32_t 
     }
 }
 
-// The view of a payload slice that holds stream bytes [base, base + payload_bytes): stream bit p is
-// bit p + bit_adj of `words`, whose word 0 lies below the slice when base > 0.
-inline void fill_range_view(RangeDecArgs& a, SeekArgs& y, const Tables& t, const uint8_t* d_payload,
-                            uint64_t payload_bytes, uint64_t base, uint64_t nsym) {
-    fill_dec_args(a, t, d_payload, payload_bytes, nsym);
-    const uint64_t head = (uintptr_t)d_payload & 63, r = base & 63;
+// The arithmetic of a moved view: stream bytes [base, base + bytes) stand at device address addr. Stream
+// bit p is bit p + bit_adj of the words at words_addr (64-byte aligned), whose word 0 lies below addr
+// when base > 0. Host and device: the slice forms fix it at the call, the gathered form per job.
+struct RangeView {
+    uint64_t words_addr;
+    uint64_t w0;       // word of the 64-byte line that holds addr
+    uint64_t head;     // addr's byte in that line
+    uint64_t nwords;   // one past the word of the last byte
+    uint64_t clamp_lo, bit_hi;
+    uint32_t bit_adj;
+};
+__host__ __device__ __forceinline__ RangeView range_view(uint64_t addr, uint64_t bytes, uint64_t base) {
+    RangeView v;
+    const uint64_t head = addr & 63, r = base & 63;
     uint64_t shift = base >> 6;  // 64-byte units the view's word 0 moves down
     uint64_t adj = head - r;
     if (head < r) { adj = head + 64 - r; shift += 1; }
-    a.words = reinterpret_cast<const uint32_t*>(((uintptr_t)d_payload & ~(uintptr_t)63) - 64 * shift);
-    a.bit_adj = (uint32_t)(8 * adj);
-    a.w_first = 16 * shift;
-    a.nwords = a.w_first + (payload_bytes + head + 3) / 4;
-    a.start0 = 0;
+    v.words_addr = (addr & ~(uint64_t)63) - 64 * shift;
+    v.bit_adj = (uint32_t)(8 * adj);
+    v.head = head;
+    v.w0 = 16 * shift;
+    v.nwords = v.w0 + (bytes + head + 3) / 4;
     // a block's staging window starts 16 bytes below the 16-byte chunk of its first bit: inside the slice
     // unless the slice starts the stream (base 0: words below the payload read as zeros, as in hz_decode)
-    const uint64_t vlo = 8 * base + a.bit_adj;
-    y.clamp_lo = base ? 128 * ((vlo + 127) / 128 + 1) - a.bit_adj : 0;
-    y.bit_hi = 8 * (base + payload_bytes);
-    if (y.clamp_lo > y.bit_hi) y.clamp_lo = y.bit_hi;  // a slice too small for any block: every block fails
+    const uint64_t vlo = 8 * base + v.bit_adj;
+    v.clamp_lo = base ? 128 * ((vlo + 127) / 128 + 1) - v.bit_adj : 0;
+    v.bit_hi = 8 * (base + bytes);
+    if (v.clamp_lo > v.bit_hi) v.clamp_lo = v.bit_hi;  // a slice too small for any block: every block fails
+    return v;
+}
+
+// The view of a payload slice that holds stream bytes [base, base + payload_bytes).
+inline void fill_range_view(RangeDecArgs& a, SeekArgs& y, const Tables& t, const uint8_t* d_payload,
+                            uint64_t payload_bytes, uint64_t base, uint64_t nsym) {
+    fill_dec_args(a, t, d_payload, payload_bytes, nsym);
+    const RangeView v = range_view((uint64_t)(uintptr_t)d_payload, payload_bytes, base);
+    a.words = reinterpret_cast<const uint32_t*>((uintptr_t)v.words_addr);
+    a.bit_adj = v.bit_adj;
+    a.w_first = v.w0;
+    a.nwords = v.nwords;
+    a.start0 = 0;
+    y.clamp_lo = v.clamp_lo;
+    y.bit_hi = v.bit_hi;
     y.nsym = nsym;
 }
 

@@ -1,14 +1,22 @@
 // hz_ranges.hip -- gfx950 (MI355X, CDNA4) batch random access: many ranges of one stream in one call
-// (hz_decode_ranges; DESIGN.md "Random access", "A batch of ranges").
+// (hz_decode_ranges, hz_decode_ranges_pieces; DESIGN.md "Random access", "A batch of ranges", "Gathered
+// pieces").
 //
 //   k_ranges_plan    per range: checks, block jobs, exclusive scan of the job counts
 //   k_ranges_decode  one wave per block job: stage, cooperative walk, decode, clipped store
+//
+// Both come in two compile-time forms. PIECES = false: one payload slice and one seek table for the whole
+// call, the view fixed by the host. PIECES = true: every range names a piece of a gathered buffer, and
+// the wave of a job builds the view of that piece (wave-uniform, in scalar registers) before it touches
+// the block; everything after that is the same code.
 //
 // The view, the per-block checks and the FIXED16 step are hz_decode.hip's (hz_range_device.h); the
 // lookup, the staged window and the bit reader are the block decoders' (hz_decode_device.h). A unit of
 // its own: its callers of that shared force-inlined code must not change what the compiler assumes
 // inside it for the kernels of hz_decode.hip (DESIGN.md "Source layout"). All integer/bit work; no MFMA.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "hz_range_device.h"
 
@@ -24,6 +32,66 @@ struct RangesArgs {
     uint32_t wave_words;       // LDS of a wave: slot, bitmap, kChainsPerBlock chain starts
 };
 
+// The gathered form: ranges that name pieces, the pieces, the buffer they sit in and the compact table.
+struct PieceRangesArgs : RangesArgs {
+    const hz_piece_range* pranges;  // device list (`ranges` is unset)
+    const hz_piece* pieces;         // device list
+    uint32_t npieces;
+    const uint8_t* buf;
+    uint64_t buf_bytes;
+    const unsigned long long* cseek;  // the words the pieces name, seek_words of them
+    uint64_t seek_words;
+};
+template <bool PIECES> using RangesArgsOf = std::conditional_t<PIECES, PieceRangesArgs, RangesArgs>;
+
+// The gathered form's decoder arguments: a type of its own, so that the bit reader's chunk loads
+// (br_init / br_word / br_next of this type) are the ld_chunk below and keep to the piece at its lower
+// end as well. The slice forms keep the shared ld_chunk, whose view ends on a 64-byte line below.
+struct PieceDecArgs : RangeDecArgs {};
+template <bool PIECES> using DecArgsOf = std::conditional_t<PIECES, PieceDecArgs, RangeDecArgs>;
+
+HZ_DEV uint4 ld_chunk(const PieceDecArgs& a, uint64_t w) {  // w % 4 == 0; zeros outside [w_first, nwords)
+    if (w >= a.w_first && w + 4 <= a.nwords) return *reinterpret_cast<const uint4*>(a.words + w);
+    uint32_t t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = w + k >= a.w_first && w + k < a.nwords ? a.words[w + k] : 0u;
+    return make_uint4(t[0], t[1], t[2], t[3]);
+}
+
+// Range i of a call's list.
+HZ_DEV hz_range range_at(const RangesArgs& p, uint64_t i) { return p.ranges[i]; }
+HZ_DEV hz_piece_range range_at(const PieceRangesArgs& p, uint64_t i) { return p.pranges[i]; }
+
+// What the plan asks of a non-empty range's piece before any job of the range exists: the piece is one of
+// the list, its bytes lie in the buffer, its table words in the compact table, its positions below
+// HZ_POS_LIMIT, and every block of the range is one of its blocks.
+HZ_DEV bool piece_ok(const PieceRangesArgs& p, const hz_piece_range& r) {
+    if (r.sym_count == 0) return true;  // an empty range names no piece
+    if (r.piece >= p.npieces) return false;
+    const hz_piece pc = p.pieces[r.piece];
+    constexpr uint64_t kMaxByte = (HZ_POS_LIMIT - 1) / 8;  // 8 * byte < HZ_POS_LIMIT
+    const uint64_t b0 = r.sym_begin / kBlockSyms, b1 = (r.sym_begin + r.sym_count - 1) / kBlockSyms;
+    return pc.bytes <= p.buf_bytes && pc.buf_byte <= p.buf_bytes - pc.bytes && pc.nblocks < p.seek_words &&
+           pc.seek_index <= p.seek_words - pc.nblocks - 1 && b0 >= pc.first_block && b1 - pc.first_block < pc.nblocks &&
+           pc.stream_byte <= kMaxByte && pc.bytes <= kMaxByte - pc.stream_byte;
+}
+
+// The view of a job's piece into the wave's copy of the kernel arguments: fill_range_view's arithmetic on
+// the piece's place in the buffer, its first existing word the one that holds the piece's first byte, and
+// the table addressed so that block b of the stream stands at seek[b]. All of it is wave-uniform.
+HZ_DEV void piece_view(RangeDecArgs& a, SeekArgs& y, const PieceRangesArgs& p, const hz_piece& pc) {
+    const RangeView v = range_view((uint64_t)reinterpret_cast<uintptr_t>(p.buf) + pc.buf_byte, pc.bytes, pc.stream_byte);
+    // through a global-address-space pointer: from a bare integer the compiler cannot tell, and every
+    // payload load of the kernel would be a flat load
+    a.words = (const uint32_t*)reinterpret_cast<const __attribute__((address_space(1))) uint32_t*>((uintptr_t)v.words_addr);
+    a.bit_adj = v.bit_adj;
+    a.w_first = v.w0 + v.head / 4;
+    a.nwords = v.nwords;
+    y.clamp_lo = v.clamp_lo;
+    y.bit_hi = v.bit_hi;
+    y.seek = p.cseek + pc.seek_index - pc.first_block;
+}
+
 constexpr int kPlanThreads = 1024;
 constexpr int kRangesMaxWaves = 16;
 constexpr uint32_t kRangesMaxRounds = 64;  // lane i holds the true path after round i at the latest
@@ -32,7 +100,8 @@ constexpr uint32_t kDead = 0xffffffffu;    // exit of a path that met an invalid
 // Jobs of a range = the blocks it touches (none for an empty or a refused one). One workgroup takes the
 // list 1024 ranges at a time and carries the running sum, so any length takes nranges + 1 words of
 // scratch and one launch (launch_scan would need the counts and its tile sums beside the offsets).
-__global__ __launch_bounds__(kPlanThreads) void k_ranges_plan(RangesArgs p, uint64_t nsym, uint32_t* err) {
+template <bool PIECES>
+__global__ __launch_bounds__(kPlanThreads) void k_ranges_plan(RangesArgsOf<PIECES> p, uint64_t nsym, uint32_t* err) {
     __shared__ uint64_t sh[kPlanThreads / 64 + 1];
     uint64_t carry = 0;
     bool refused = false;
@@ -40,9 +109,12 @@ __global__ __launch_bounds__(kPlanThreads) void k_ranges_plan(RangesArgs p, uint
         const uint64_t i = i0 + threadIdx.x;
         uint64_t nb = 0;
         if (i < p.nranges) {
-            const hz_range r = p.ranges[i];
-            const bool ok = r.sym_begin <= nsym && r.sym_count <= nsym - r.sym_begin && !(r.out_byte & 1) &&
-                            r.out_byte <= p.out_bytes && 2 * r.sym_count <= p.out_bytes - r.out_byte;
+            const auto r = range_at(p, i);
+            bool ok = r.sym_begin <= nsym && r.sym_count <= nsym - r.sym_begin && !(r.out_byte & 1) &&
+                      r.out_byte <= p.out_bytes && 2 * r.sym_count <= p.out_bytes - r.out_byte;
+            if constexpr (PIECES) {
+                if (ok) ok = piece_ok(p, r);
+            }
             refused |= !ok;
             if (ok && r.sym_count) nb = (r.sym_begin + r.sym_count - 1) / kBlockSyms - r.sym_begin / kBlockSyms + 1;
         }
@@ -154,10 +226,10 @@ HZ_DEV bool coop_starts(const DecArgs& a, const uint32_t* lds, const uint32_t* s
 }
 
 // The cold path's chain starts: lane 0 walks the block's cnt codewords over global memory as
-// k_seek_subs does (the reader clamps its loads to the view; the walk stops at cnt codewords or past
+// k_seek_subs does (the reader clamps its loads to the view, A's ld_chunk; the walk stops at cnt codewords or past
 // bit n, whichever comes first).
-template <int MODE>
-HZ_DEV bool cold_starts(const DecArgs& a, const uint32_t* lds, uint64_t s0, uint32_t n, uint32_t cnt, uint32_t* cs,
+template <int MODE, typename A>
+HZ_DEV bool cold_starts(const A& a, const uint32_t* lds, uint64_t s0, uint32_t n, uint32_t cnt, uint32_t* cs,
                         int lane) {
     uint32_t ok = 0;
     if (lane == 0) {
@@ -182,8 +254,10 @@ HZ_DEV bool cold_starts(const DecArgs& a, const uint32_t* lds, uint64_t s0, uint
 // payload slot, a boundary bitmap of as many words and 256 chain starts. A block whose staging window
 // does not fit the slot takes the cold path (a wave-uniform branch): one lane finds the chain starts over
 // global memory and every lane decodes its chains through its own bit reader.
-template <int MODE, bool WIDE>
-__global__ __launch_bounds__(kRangesMaxWaves * 64) void k_ranges_decode(RangeDecArgs a, SeekArgs y, RangesArgs p) {
+// PIECES: the view (a.words, a.bit_adj, a.w_first, a.nwords, y.clamp_lo, y.bit_hi, y.seek) is the job's
+// piece's, rebuilt per job in the wave's own copy of the arguments.
+template <int MODE, bool WIDE, bool PIECES>
+__global__ __launch_bounds__(kRangesMaxWaves * 64) void k_ranges_decode(DecArgsOf<PIECES> a, SeekArgs y, RangesArgsOf<PIECES> p) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint64_t total = p.offs[p.nranges];
     const uint32_t nw = blockDim.x >> 6;
@@ -203,7 +277,8 @@ __global__ __launch_bounds__(kRangesMaxWaves * 64) void k_ranges_decode(RangeDec
             if (p.offs[mid] <= j) ri = mid;
             else rh = mid;
         }
-        const hz_range rg = p.ranges[ri];
+        const auto rg = range_at(p, ri);
+        if constexpr (PIECES) piece_view(a, y, p, p.pieces[rg.piece]);
         const uint64_t lo = rg.sym_begin, hi = rg.sym_begin + rg.sym_count;
         const uint64_t b = lo / kBlockSyms + (j - p.offs[ri]);
         const uint64_t s0 = y.seek[b], s1 = y.seek[b + 1];
@@ -376,14 +451,46 @@ static uint32_t ranges_slot_override() {
 
 uint64_t ranges_scratch_words(uint32_t nranges) { return (uint64_t)nranges + 2; }
 
-template <int MODE, bool WIDE>
-static hipError_t ranges_launch(const RangeDecArgs& a, const SeekArgs& y, const RangesArgs& p, int waves, uint32_t lds_bytes,
-                                int ncu, hipStream_t s) {
-    hipError_t e = ensure_lds_limit((const void*)k_ranges_decode<MODE, WIDE>, kLdsBytes);
+template <int MODE, bool WIDE, bool PIECES>
+static hipError_t ranges_launch(const DecArgsOf<PIECES>& a, const SeekArgs& y, const RangesArgsOf<PIECES>& p, int waves,
+                                uint32_t lds_bytes, int ncu, hipStream_t s) {
+    hipError_t e = ensure_lds_limit((const void*)k_ranges_decode<MODE, WIDE, PIECES>, kLdsBytes);
     if (e != hipSuccess) return e;
     const uint32_t per_cu = kLdsBytes / lds_bytes < 2 ? 1 : 2;
-    hipLaunchKernelGGL((k_ranges_decode<MODE, WIDE>), dim3((uint32_t)ncu * per_cu), dim3(64 * waves), lds_bytes, s, a, y, p);
+    hipLaunchKernelGGL((k_ranges_decode<MODE, WIDE, PIECES>), dim3((uint32_t)ncu * per_cu), dim3(64 * waves), lds_bytes, s, a, y, p);
     return hipGetLastError();
+}
+
+// The plan, then the decode kernel of the codebook's table mode with its slots sized (both forms).
+template <bool PIECES>
+static hipError_t ranges_run(const Tables& t, const DecArgsOf<PIECES>& a, const SeekArgs& y, RangesArgsOf<PIECES>& p, uint64_t nsym,
+                             uint32_t* d_err, int ncu, hipStream_t s) {
+    hipError_t e;
+    hipLaunchKernelGGL(k_ranges_plan<PIECES>, dim3(1), dim3(kPlanThreads), 0, s, p, nsym, d_err);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const uint32_t table = a.lds_words, room = kLdsBytes / 4;
+    if (t.dec_mode == DEC_FIXED16) {  // positions are arithmetic: no slot, no walk
+        return ranges_launch<DEC_FIXED16, false, PIECES>(a, y, p, kRangesMaxWaves, 4 * table, ncu, s);
+    }
+    // slots for the codebook's mean block with headroom, as run_decode sizes them; the largest that fits
+    // beside the table when not even one such wave does
+    const double avg = t.dec_avg_bits > (double)t.dec_min_len ? t.dec_avg_bits : (double)(t.dec_min_len > 0 ? t.dec_min_len : 1);
+    const uint64_t bits = (uint64_t)(avg * (double)kBlockSyms);
+    const uint32_t worst = dec_slot_words_max(a.max_len);
+    uint32_t slot = dec_slot_words(bits + bits / 16 + 256, a.max_len);
+    slot = slot < worst ? slot : worst;
+    if (ranges_slot_override()) slot = ranges_slot_override();
+    if (table + kChainsPerBlock + 8 > room) return hipErrorInvalidValue;
+    const uint32_t fit = ((room - table - kChainsPerBlock) / 2) & ~3u;
+    slot = slot < fit ? slot : fit;
+    p.slot_words = slot;
+    p.wave_words = 2 * slot + kChainsPerBlock;
+    uint32_t waves = (room - table) / p.wave_words;
+    waves = waves < (uint32_t)kRangesMaxWaves ? waves : (uint32_t)kRangesMaxWaves;
+    const uint32_t lds_bytes = 4 * (table + waves * p.wave_words);
+    if (t.dec_mode == DEC_DENSE) return ranges_launch<DEC_DENSE, false, PIECES>(a, y, p, (int)waves, lds_bytes, ncu, s);
+    if (t.dec_max_len > 32) return ranges_launch<DEC_LUT, true, PIECES>(a, y, p, (int)waves, lds_bytes, ncu, s);
+    return ranges_launch<DEC_LUT, false, PIECES>(a, y, p, (int)waves, lds_bytes, ncu, s);
 }
 
 hipError_t launch_decode_ranges(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t base,
@@ -402,31 +509,28 @@ hipError_t launch_decode_ranges(const Tables& t, const uint8_t* d_payload, uint6
     y.isub = full_index && t.dec_mode != DEC_FIXED16 ? d_seek + index_sub_offset(index_blocks(nsym)) : nullptr;
     RangesArgs p{};
     p.ranges = d_ranges; p.nranges = nranges; p.offs = d_scratch; p.out_bytes = out_bytes; p.stats = d_stats;
-    hipLaunchKernelGGL(k_ranges_plan, dim3(1), dim3(kPlanThreads), 0, s, p, nsym, d_err);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t table = a.lds_words, room = kLdsBytes / 4;
-    if (t.dec_mode == DEC_FIXED16) {  // positions are arithmetic: no slot, no walk
-        return ranges_launch<DEC_FIXED16, false>(a, y, p, kRangesMaxWaves, 4 * table, ncu, s);
-    }
-    // slots for the codebook's mean block with headroom, as run_decode sizes them; the largest that fits
-    // beside the table when not even one such wave does
-    const double avg = t.dec_avg_bits > (double)t.dec_min_len ? t.dec_avg_bits : (double)(t.dec_min_len > 0 ? t.dec_min_len : 1);
-    const uint64_t bits = (uint64_t)(avg * (double)kBlockSyms);
-    const uint32_t worst = dec_slot_words_max(a.max_len);
-    uint32_t slot = dec_slot_words(bits + bits / 16 + 256, a.max_len);
-    slot = slot < worst ? slot : worst;
-    if (ranges_slot_override()) slot = ranges_slot_override();
-    if (table + kChainsPerBlock + 8 > room) return hipErrorInvalidValue;
-    const uint32_t fit = ((room - table - kChainsPerBlock) / 2) & ~3u;
-    slot = slot < fit ? slot : fit;
-    p.slot_words = slot;
-    p.wave_words = 2 * slot + kChainsPerBlock;
-    uint32_t waves = (room - table) / p.wave_words;
-    waves = waves < (uint32_t)kRangesMaxWaves ? waves : (uint32_t)kRangesMaxWaves;
-    const uint32_t lds_bytes = 4 * (table + waves * p.wave_words);
-    if (t.dec_mode == DEC_DENSE) return ranges_launch<DEC_DENSE, false>(a, y, p, (int)waves, lds_bytes, ncu, s);
-    if (t.dec_max_len > 32) return ranges_launch<DEC_LUT, true>(a, y, p, (int)waves, lds_bytes, ncu, s);
-    return ranges_launch<DEC_LUT, false>(a, y, p, (int)waves, lds_bytes, ncu, s);
+    return ranges_run<false>(t, a, y, p, nsym, d_err, ncu, s);
+}
+
+hipError_t launch_decode_ranges_pieces(const Tables& t, const uint8_t* d_buf, uint64_t buf_bytes,
+                                       const unsigned long long* d_seek, uint64_t seek_words, const hz_piece* d_pieces,
+                                       uint32_t npieces, uint64_t nsym, const hz_piece_range* d_ranges, uint32_t nranges,
+                                       uint8_t* d_out, uint64_t out_bytes, unsigned long long* d_stats,
+                                       unsigned long long* d_scratch, uint32_t* d_err, int ncu, hipStream_t s) {
+    hipError_t e;
+    if (d_stats && (e = hipMemsetAsync(d_stats, 0, 8 * HZ_RANGES_STATS_WORDS, s)) != hipSuccess) return e;
+    if (nranges == 0) return hipSuccess;
+    PieceDecArgs a{};
+    SeekArgs y{};
+    fill_dec_args(a, t, d_buf, buf_bytes, nsym);  // the tables; every job sets its own view (piece_view)
+    a.start0 = 0;
+    a.out = d_out; a.err = d_err;
+    y.nsym = nsym;
+    PieceRangesArgs p{};
+    p.pranges = d_ranges; p.nranges = nranges; p.offs = d_scratch; p.out_bytes = out_bytes; p.stats = d_stats;
+    p.pieces = d_pieces; p.npieces = npieces; p.buf = d_buf; p.buf_bytes = buf_bytes;
+    p.cseek = d_seek; p.seek_words = seek_words;
+    return ranges_run<true>(t, a, y, p, nsym, d_err, ncu, s);
 }
 
 }  // namespace hz

@@ -195,6 +195,22 @@ class StreamCodec:
                                full_index, payload_byte_base)
         return out
 
+    def decode_ranges_pieces(self, buf, seek, pieces, nsym, ranges, out, stats=None):
+        """A batch of ranges from gathered pieces (hz_decode_ranges_pieces). buf: the gathered payload
+        bytes (uint8, 4-byte aligned); seek: the compact table, the words the pieces name (64-bit); pieces: (k, 6) rows
+        (stream_byte, bytes, buf_byte, first_block, seek_index, nblocks); ranges: (k, 4) rows (sym_begin,
+        sym_count, out_byte, piece), all 64-bit device tensors that the call reads on the device only, so
+        a captured graph replays with whatever they hold then. huffman_amd.seek_pieces plans them."""
+        for name, t, cols in (("pieces", pieces, 6), ("ranges", ranges, 4)):
+            if t.dim() != 2 or t.shape[1] != cols or t.element_size() != 8 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous (k, {cols}) tensor of 64-bit integers")
+        if seek.element_size() != 8 or not seek.is_contiguous():
+            raise ValueError("seek: a contiguous tensor of 64-bit integers")
+        self.dev.decode_ranges_pieces(buf.data_ptr(), buf.numel(), seek.data_ptr(), seek.numel(), pieces.data_ptr(),
+                                      pieces.shape[0], nsym, ranges.data_ptr(), ranges.shape[0], out.data_ptr(),
+                                      out.numel(), None if stats is None else stats.data_ptr())
+        return out
+
     def index_expand(self, payload, nsym, seek, index):
         """The complete block index from the seek table (seek may be index itself)."""
         self.dev.index_expand(payload.data_ptr(), payload.numel(), seek.data_ptr(), nsym, index.data_ptr())

@@ -76,6 +76,8 @@ typedef struct hz_ctx hz_ctx;
  * position is HZ_POS_LIMIT or more, or does not fit 64 bits at all, returns
  * HZ_EINVAL at the call with nothing launched:
  *   hz_decode_range, hz_decode_ranges   8 * (payload_byte_base + payload_bytes)
+ *   hz_decode_ranges_pieces             8 * buf_bytes (a piece's 8 * (stream_byte +
+ *                                       bytes): found on the device, that range refused)
  *   hz_pack_seek                        bit_base + 8 * out_cap
  *   hz_decode_indexless_seek            bit_base + 8 * payload_bytes
  *   hz_indexless_scan                   payload_bit_base + 8 * payload_bytes */
@@ -336,6 +338,83 @@ int hz_decode_ranges(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_byt
                      const uint64_t *d_seek, uint64_t nsym, const hz_range *d_ranges, uint32_t nranges,
                      uint8_t *d_out, uint64_t out_bytes, uint64_t *d_stats, uint32_t flags);
 
+/* The same batch from GATHERED PIECES: instead of one slice that covers every
+ * range's span (and whatever lies between the spans), d_buf holds only the
+ * payload bytes the ranges need, as pieces, and d_seek only the table words the
+ * pieces name. Scattered reads of a large stream then move a block and its margins
+ * per range, not the hull. hz_seek_pieces plans such a buffer on the host.
+ * A PIECE is a contiguous run of the stream's payload, bytes [stream_byte,
+ * stream_byte + bytes), standing at d_buf + buf_byte, with the seek entries of
+ * blocks first_block .. first_block + nblocks (nblocks + 1 words, contiguous) at
+ * d_seek[seek_index ...]. A range names the piece that holds its span (several
+ * ranges may name one piece); everything else of a range means what it means for
+ * hz_decode_ranges, and so do nsym, d_out, out_bytes and d_stats.
+ * d_pieces and d_ranges are DEVICE arrays that the host never reads: the call is
+ * stream-ordered and capturable, and a captured graph can be replayed after new
+ * pieces, ranges, buffer bytes and table words have been written into the same
+ * arrays (entries not in use: sym_count 0, which names no piece).
+ * The wave of a block builds the view of its range's piece before it touches the
+ * block (DESIGN.md "Gathered pieces"). buf_byte and stream_byte may have any
+ * congruence (hz_seek_pieces keeps them equal modulo 64, which keeps the 16-byte
+ * staging loads whole). A piece whose stream_byte is 0 starts the stream: its first
+ * block needs no margin below. For every other piece, and above, the margins are
+ * hz_seek_span's, clamped to the payload's end.
+ * flags must be 0 (a full index has no gathered form). Needs the decode tables and
+ * nranges + 2 u64 of the context's scratch: ends a pending index-less part like
+ * every scratch user, and the host waits only when the scratch must grow.
+ * HZ_EINVAL at the call, nothing launched: null pointers (d_stats may be null),
+ * nonzero flags, an odd d_out, a d_buf that is not 4-byte aligned, no decode
+ * tables, 8 * buf_bytes not below HZ_POS_LIMIT. nranges 0: HZ_OK, nothing launched (d_stats is left as it was).
+ * Found on the device and reported by hz_ctx_sync as HZ_EINVAL, with nothing
+ * written for the range concerned and every other range decoded: what
+ * hz_decode_ranges refuses a range for; piece >= npieces; buf_byte + bytes >
+ * buf_bytes; seek_index + nblocks + 1 > seek_words; a block of the range outside
+ * [first_block, first_block + nblocks); 8 * (stream_byte + bytes) not below
+ * HZ_POS_LIMIT or not fitting 64 bits. Per block, against the piece: HZ_EINVAL
+ * for a block whose bytes and margins are not inside the piece, HZ_EFORMAT for
+ * what hz_decode_ranges reports it for (a flagged block stores nothing).
+ * No load of a block leaves its piece's bytes rounded out to 4-byte words, on the
+ * cold path's bit readers included; words of a 16-byte chunk outside the piece
+ * read as zeros. So no load leaves [d_buf, d_buf + buf_bytes) rounded up to a
+ * 4-byte word (d_buf is 4-byte aligned: the call refuses another). */
+typedef struct hz_piece {
+    uint64_t stream_byte;  /* payload byte of the stream its first byte is */
+    uint64_t bytes;        /* its length */
+    uint64_t buf_byte;     /* where it sits in d_buf */
+    uint64_t first_block;  /* the block whose seek entry stands at d_seek[seek_index] */
+    uint64_t seek_index;   /* entries first_block .. first_block + nblocks at d_seek[seek_index ...] */
+    uint64_t nblocks;      /* blocks whose entries (nblocks + 1 words) the piece carries */
+} hz_piece;
+typedef struct hz_piece_range {
+    uint64_t sym_begin, sym_count, out_byte;  /* hz_range's */
+    uint64_t piece;                           /* index into d_pieces (not read when sym_count is 0) */
+} hz_piece_range;
+int hz_decode_ranges_pieces(hz_ctx *ctx, const uint8_t *d_buf, uint64_t buf_bytes,
+                            const uint64_t *d_seek, uint64_t seek_words,
+                            const hz_piece *d_pieces, uint32_t npieces, uint64_t nsym,
+                            const hz_piece_range *d_ranges, uint32_t nranges,
+                            uint8_t *d_out, uint64_t out_bytes, uint64_t *d_stats, uint32_t flags);
+
+/* Host arithmetic on a HOST seek table, beside hz_seek_span: the plan of a gathered
+ * buffer for a list of ranges. Every non-empty range's hz_seek_span, clamped to
+ * payload_bytes, is taken; spans that overlap or touch merge into one piece. Pieces
+ * come out in ascending stream_byte, disjoint and not touching; piece k stands at
+ * buf_byte = (end of piece k - 1, rounded up to 64) + (stream_byte & 63), so every
+ * piece is congruent to its stream position modulo 64; *buf_bytes is the end of the
+ * last piece rounded up to 16. A piece carries the seek entries of the hull of its
+ * ranges' blocks: seek_index counts up in piece order and *seek_words is the total
+ * (the caller gathers seek[first_block .. first_block + nblocks] to seek_index).
+ * out[i] is ranges[i] with its piece (an empty range: piece 0, which nothing reads).
+ * pieces has room for nranges entries; *npieces receives their number. The sum of
+ * the pieces' bytes is at most the sum of the spans', and *buf_bytes at most that
+ * sum + 128 * *npieces. HZ_EINVAL: what hz_seek_span refuses, null outputs (ranges,
+ * pieces and out may be null when nranges is 0, which gives zeros). HZ_EFORMAT: a
+ * span that starts at or past payload_bytes (the table is not this payload's). */
+int hz_seek_pieces(const uint64_t *seek, uint64_t nsym, uint64_t payload_bytes,
+                   const hz_range *ranges, uint32_t nranges,
+                   hz_piece *pieces, uint32_t *npieces,
+                   hz_piece_range *out, uint64_t *buf_bytes, uint64_t *seek_words);
+
 /* Expand a seek table into the complete block index of the stream (start[] copied,
  * max_bits and sub[] computed, chains past the end as hz_pack writes them): byte for
  * byte what hz_pack / hz_index_build write. d_payload is the whole payload;
@@ -588,7 +667,19 @@ int hz_encode_host_seek(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t ca
  * hz_decode_ranges_host: nranges byte ranges [offsets[i], offsets[i] + counts[i])
  * in one hz_decode_ranges call, their bytes concatenated in out in list order; one
  * payload slice goes to the device, from the smallest byte_begin to the largest
- * byte_end of the ranges' spans (whatever lies between them included). */
+ * byte_end of the ranges' spans (whatever lies between them included).
+ * hz_decode_ranges_host_pieces: the same bytes for the same arguments, from gathered
+ * pieces: hz_seek_pieces' plan, one staging buffer of its buf_bytes with each piece
+ * copied in, the compact table, one hz_decode_ranges_pieces call. What goes to the
+ * device is buf_bytes + 8 * seek_words + the two lists, whatever lies between the
+ * ranges. hz_decode_ranges_file: that flow on a file on disk, as
+ * hz_decode_range_file reads one range: the header (at most 1 MiB) and each piece's
+ * bytes are read (pread), nothing else. A missing file: HZ_ENOENT before any device
+ * call. Both: a span that starts at or past the payload's end: HZ_EFORMAT. */
+int hz_decode_ranges_host_pieces(const uint8_t *file, uint64_t len, const uint64_t *seek, const uint64_t *offsets,
+                                 const uint64_t *counts, uint32_t nranges, uint8_t *out);
+int hz_decode_ranges_file(const char *path, const uint64_t *seek, const uint64_t *offsets,
+                          const uint64_t *counts, uint32_t nranges, uint8_t *out);
 int hz_decode_ranges_host(const uint8_t *file, uint64_t len, const uint64_t *seek, const uint64_t *offsets,
                           const uint64_t *counts, uint32_t nranges, uint8_t *out);
 int hz_seek_build_host(const uint8_t *file, uint64_t len, uint64_t *seek, uint64_t cap_bytes, uint64_t *nsym);
