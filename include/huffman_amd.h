@@ -96,6 +96,8 @@ int hz_ctx_sync(hz_ctx *ctx);
 
 /* 65 536-bin histogram of the u16 symbols of d_in[0..n) into d_hist (u64 x
  * 65536); accumulate != 0 adds to d_hist instead of overwriting.
+ * Stream-ordered, no host synchronisation and no scratch: a HIP graph can capture
+ * it and replay it on whatever d_in holds then.
  * Replaces calculateFrequency (Compressor.cu:38-48, launch :369-372). */
 int hz_hist16(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_hist, int accumulate);
 
@@ -109,7 +111,13 @@ int hz_codebook_build(const uint64_t *hist, hz_codebook *cb);
  * device) -> d_cb (a device buffer of sizeof(hz_codebook), the same layout),
  * stream-ordered on the context's stream, one workgroup, GenerateCL's rounds
  * (gpuHuffmanConstruction.h:353-494) without a grid barrier. Errors surface at
- * hz_ctx_sync: HZ_EINVAL (a count >= 2^47), HZ_ETOOLONG (a code > HZ_MAXLEN). */
+ * hz_ctx_sync: HZ_EINVAL (a count >= 2^47), HZ_ETOOLONG (a code > HZ_MAXLEN).
+ * This call, hz_header_write_device and hz_header_parse_device share one workspace
+ * of the context, allocated by the first of them (the one host wait). No result
+ * depends on what an earlier call left there (tests/test_gpu_second_use.py: U =
+ * 65 536, then 3, then 1 without a synchronisation), so the calls may follow one
+ * another in stream order, and after that first call a HIP graph can capture them
+ * and replay them on whatever d_hist, d_cb and d_file hold then. */
 int hz_codebook_build_device(hz_ctx *ctx, const uint64_t *d_hist, hz_codebook *d_cb);
 
 /* Header bit length for a codebook and input size: 8*(3 + odd) + sum(24 + L) + 64.
@@ -190,7 +198,9 @@ uint64_t hz_scratch_bytes(uint64_t nsym);
  * `start_bit` of d_out (d_out 4-byte aligned; bits of d_out's first word before start_bit are taken from `lead`,
  * right aligned, i.e. the header's pending bits). Bits after the stream's end
  * up to the next 32-bit word are zero. d_index (optional, hz_index_bytes())
- * receives the block index. Replaces
+ * receives the block index. Stream-ordered and capturable by a HIP graph (it
+ * replays on whatever d_in holds then); the host waits only when the context's
+ * scratch must grow. Replaces
  * populateCWLength + transform_inclusive_scan + encodeFromCW
  * (Compressor.cu:50-61,541-576,182-313) and writeFileContent (:673-684,597-601). */
 int hz_pack(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t start_bit, uint32_t lead,
@@ -225,6 +235,8 @@ int hz_last_pack_ranges(hz_ctx *ctx);
  * d_out (2*nsym bytes, 16-byte aligned). d_index: the block index (from
  * hz_pack, or hz_index_build for an index-less stream). d_payload
  * must stay readable up to the next 4-byte boundary after payload_bytes.
+ * Stream-ordered, no host synchronisation and no scratch: a HIP graph can capture
+ * it and replay it on whatever d_payload and d_index hold then.
  * Replaces translateFile (Decompressor.cu:259-291). */
 int hz_decode(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t nsym,
               const uint64_t *d_index, uint8_t *d_out);
@@ -235,7 +247,10 @@ int hz_last_decode_chunks(hz_ctx *ctx);
 
 /* Build the block index of an index-less stream (a .compressed file from
  * the reference encoder) on the device. If the payload holds fewer than nsym
- * codewords, start[nblocks] (the end bit) is left at UINT64_MAX. */
+ * codewords, start[nblocks] (the end bit) is left at UINT64_MAX.
+ * NOT capturable: the host waits for the stream after every fix-up round (it
+ * reads whether a round changed anything). Under stream capture use
+ * hz_seek_build and hz_index_expand, which are stream-ordered. */
 int hz_index_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
                    uint64_t nsym, uint64_t *d_index);
 
@@ -419,7 +434,7 @@ int hz_seek_pieces(const uint64_t *seek, uint64_t nsym, uint64_t payload_bytes,
  * max_bits and sub[] computed, chains past the end as hz_pack writes them): byte for
  * byte what hz_pack / hz_index_build write. d_payload is the whole payload;
  * d_index holds hz_index_bytes(nsym); d_seek and d_index may be the same pointer.
- * Stream-ordered, no scratch. A block that fails hz_decode_range's checks leaves
+ * Stream-ordered and capturable, no scratch. A block that fails hz_decode_range's checks leaves
  * its sub[] row unwritten and reports HZ_EFORMAT / HZ_EINVAL at hz_ctx_sync. */
 int hz_index_expand(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, const uint64_t *d_seek,
                     uint64_t nsym, uint64_t *d_index);
