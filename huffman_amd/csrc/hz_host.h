@@ -51,6 +51,11 @@ struct DevBuf {
     int alloc(size_t n) { return hipMalloc(&p, n ? n : 16) == hipSuccess ? HZ_OK : HZ_ENOMEM; }
 };
 
+// No file header is longer: 12 + 65 536 x (3 + 8) bytes, and the device writer stores whole words. What
+// the by-path calls read of a file before they parse it, and the device header writer's buffer.
+constexpr uint64_t kMaxHeaderBytes = 1u << 20;
+static_assert(kMaxHeaderBytes >= 12 + 65536ull * 11 + 4, "the longest header, in whole words");
+
 // The process-wide context of the hz_*_host and file calls (created on first use, device 0).
 int default_ctx(hz_ctx** out);
 

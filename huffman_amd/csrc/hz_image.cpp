@@ -1,17 +1,16 @@
 // hz_image.cpp -- the whole-buffer flows behind hz_*_host (used by the tests and the Python package): a
 // complete .compressed image in host memory encoded, decoded, indexed and decoded by ranges on the
 // process-wide context, device work inside.
-#include <fcntl.h>
 #include <stdint.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <memory>
 #include <vector>
 
+#include "hz_file_io.h"
 #include "hz_host.h"
+#include "hz_stream_plan.h"
 
 using namespace hz;
 
@@ -93,8 +92,8 @@ int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint3
 // a file on disk (open_file) of which only the header and the payload bytes asked for are read.
 struct OpenedImage {
     const uint8_t* f = nullptr;
-    int fd = -1;                    // open_file: the file
-    std::vector<uint8_t> head;      // open_file: its first bytes (the header is at most 12 + 65536 * 11 bytes)
+    FileReader file{nullptr};       // open_file: the file (its reads are untimed)
+    std::vector<uint8_t> head;      // open_file: its first bytes (kMaxHeaderBytes holds every header)
     // open_file: the payload bytes of the last upload. The async copy reads them until the caller's next
     // hz_ctx_sync, so an image takes ONE upload per flow (every flow here does) and outlives that sync;
     // mutable because upload() is const for the in-memory form, which needs no buffer
@@ -112,36 +111,22 @@ struct OpenedImage {
         pay = len - info.payload_byte;
         return HZ_OK;
     }
-    ~OpenedImage() { if (fd >= 0) ::close(fd); }
     int open_file(const char* path) {
-        struct stat st;
-        if (stat(path, &st) != 0) return HZ_ENOENT;
-        fd = ::open(path, O_RDONLY);
-        if (fd < 0) return HZ_EIO;
-        const uint64_t fsize = (uint64_t)st.st_size;
-        head.resize(std::min<uint64_t>(fsize, 1u << 20));
-        int rc = read_at(head.data(), head.size(), 0);
+        int rc = file.open(path);
         if (rc) return rc;
+        const uint64_t fsize = file.size();
+        head.resize(std::min<uint64_t>(fsize, kMaxHeaderBytes));
+        if ((rc = read_at(head.data(), head.size(), 0))) return rc;
         if ((rc = hz_header_parse(head.data(), head.size(), cb.get(), &info))) return rc;
         if (info.payload_byte > fsize) return HZ_EFORMAT;
         nsym = info.n / 2;
         pay = fsize - info.payload_byte;
         return HZ_OK;
     }
-    int read_at(uint8_t* dst, uint64_t n, uint64_t off) const {
-        for (uint64_t done = 0; done < n;) {
-            const ssize_t r = ::pread(fd, dst + done, n - done, (off_t)(off + done));
-            if (r <= 0) return HZ_EIO;
-            done += (uint64_t)r;
-        }
-        return HZ_OK;
-    }
-    // every codeword is >= min_len bits: a header claiming more symbols than the
-    // payload can hold is malformed (checked before anything is allocated)
-    bool holds_its_symbols() const {
-        const uint64_t pay_bits = pay * 8 > info.payload_bit ? pay * 8 - info.payload_bit : 0;
-        return nsym <= pay_bits / std::max<uint32_t>(cb->min_len, 1);
-    }
+    // on the calling thread whatever the size (parallel piece reads are open: DESIGN.md section 10, item 6)
+    int read_at(uint8_t* dst, uint64_t n, uint64_t off) const { return pread_all(file.fd(), dst, n, off); }
+    // a header claiming more symbols than the payload can hold is malformed (checked before anything is allocated)
+    bool holds_its_symbols() const { return payload_holds(pay, info.payload_bit, nsym, cb->min_len); }
     // payload bytes [b, e) to the device, with 16 zero bytes behind them
     int upload(hz_ctx* c, uint64_t b, uint64_t e, DevBuf& d) const {
         const int rc = d.alloc(e - b + 16);
