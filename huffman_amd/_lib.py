@@ -17,19 +17,27 @@ HZ_RANGE_LEAD_BYTES = 32
 HZ_RANGE_TAIL_BYTES = 32
 HZ_RANGE_FULL_INDEX = 1
 HZ_RANGES_STATS_WORDS = 4
+HZ_SUM_BLOCK_BYTES = 4096   # one block checksum per seek-table block of output
+HZ_SEEKABLE_FOOTER_BYTES = 64
+HZ_SEEKABLE_SUMS = 1        # writers: store block sums
+HZ_SEEKABLE_VERIFY = 2      # readers: check every decoded block against its sum
 HZ_POS_LIMIT = (1 << 64) - 1 - 0xFFFF  # every stream position a base-taking call reaches stays below it
 
 STATUS = {
     0: "HZ_OK", -1: "HZ_EINVAL", -2: "HZ_ENOMEM", -3: "HZ_EHIP", -4: "HZ_ETOOLONG",
     -5: "HZ_EFORMAT", -6: "HZ_ECAP", -7: "HZ_ETIMEOUT", -8: "HZ_EIO", -9: "HZ_ENODEV", -10: "HZ_ENOENT",
+    -11: "HZ_ECHECKSUM",
 }
+HZ_ECHECKSUM = -11
 STAGE_HIST, STAGE_PACK, STAGE_DECODE, STAGE_INDEX, STAGE_EXTRACT = 0, 1, 2, 3, 4
 
 
 class HZError(RuntimeError):
-    def __init__(self, status, where=""):
+    def __init__(self, status, where="", block=None):
         self.status = status
-        super().__init__(f"{where}: {STATUS.get(status, status)} ({_strerror(status)})")
+        self.block = block  # HZ_ECHECKSUM: the smallest block that does not match its stored sum
+        at = "" if block is None else f", block {block}"
+        super().__init__(f"{where}: {STATUS.get(status, status)} ({_strerror(status)}{at})")
 
 
 class Codebook(ctypes.Structure):
@@ -78,6 +86,15 @@ class Piece(ctypes.Structure):
 class PieceRange(ctypes.Structure):
     """hz_piece_range: hz_range plus the piece that holds the range's span."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("sym_begin", "sym_count", "out_byte", "piece")]
+
+
+class SeekableInfo(ctypes.Structure):
+    """hz_seekable_info: the parsed footer of a seekable file's trailer (present = 0: a plain file)."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("present", "version", "flags", "reserved")] + \
+        [(n, ctypes.c_uint64) for n in ("n", "nsym", "nblocks", "image_bytes", "seek_off", "sums_off", "file_bytes")]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
 # (name, restype, argtypes): exactly the entry points include/huffman_amd.h declares.
@@ -149,6 +166,18 @@ PROTOTYPES = [
     ("hz_decode_ranges_host", _I, [_P, _U64, _P, _P, _P, _U32, _P]),
     ("hz_decode_ranges_host_pieces", _I, [_P, _U64, _P, _P, _P, _U32, _P]),
     ("hz_decode_ranges_file", _I, [ctypes.c_char_p, _P, _P, _P, _U32, _P]),
+    ("hz_block_sums_bytes", _U64, [_U64]),
+    ("hz_block_sums", _I, [_P, _P, _U64, _P]),
+    ("hz_seekable_trailer_bytes", _U64, [_U64, _U64, _U32]),
+    ("hz_seekable_trailer_write", _I, [_U64, _U64, _P, _P, _U32, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_seekable_footer_parse", _I, [_P, _U64, ctypes.POINTER(SeekableInfo)]),
+    ("hz_seekable_info_file", _I, [ctypes.c_char_p, ctypes.POINTER(SeekableInfo)]),
+    ("hz_seekable_load_file", _I, [ctypes.c_char_p, _P, _U64, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hz_encode_host_seekable", _I, [_P, _U64, _P, _U64, ctypes.POINTER(_U64), _U32]),
+    ("hz_archive_stream_seekable", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I, _U32]),
+    ("hz_seekable_read_host", _I, [_P, _U64, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U64)]),
+    ("hz_seekable_read_file", _I, [ctypes.c_char_p, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U64)]),
+    ("hz_seekable_verify_file", _I, [ctypes.c_char_p, ctypes.POINTER(_U64)]),
 ]
 
 _lib = None

@@ -68,7 +68,7 @@ def decode(blob):
     """.compressed image -> original bytes (what `extract` writes)."""
     lib = load()
     arr, p = _buf(blob)
-    cb, info = parse_header(arr)
+    cb, info = parse_header(_image(arr))
     n_out = 2 * (info.n // 2) + (1 if info.is_odd else 0)
     out = np.empty(max(n_out, 1), dtype=np.uint8)
     got = ctypes.c_uint64()
@@ -233,7 +233,7 @@ def build_seek(blob):
     that holds the first payload bit). Works on files the reference wrote."""
     lib = load()
     arr, p = _buf(blob)
-    _, info = parse_header(arr)
+    _, info = parse_header(_image(arr))
     seek = np.zeros(max(seek_bytes(info.n // 2) // 8, 1), dtype=np.uint64)
     nsym = ctypes.c_uint64()
     check(lib.hz_seek_build_host(p, arr.size, seek.ctypes.data_as(ctypes.c_void_p), seek.size * 8, ctypes.byref(nsym)),
@@ -331,6 +331,121 @@ def decode_ranges_file(path, seek, ranges):
     return _split(out, cnts)
 
 
+# ---- seekable files: the seek table and block checksums in a trailer behind the image ----------------
+def block_sums_bytes(n):
+    """Bytes of the block sums of n bytes: one u32 per 4096 (hz_block_sums_bytes)."""
+    return load().hz_block_sums_bytes(n)
+
+
+def _image(arr):
+    """The .compressed image of a file's bytes: all of them, or what stands before a seekable trailer (a
+    header without symbols is told from one with 65 536 by where the image ends)."""
+    info = seekable_info(arr)
+    return arr if info is None else arr[:info["image_bytes"]]
+
+
+def _seekable_flags(sums):
+    return _lib.HZ_SEEKABLE_SUMS if sums else 0
+
+
+def encode_seekable(data, sums=True):
+    """Bytes -> a seekable .compressed image: encode()'s bytes, then a trailer with the writer's seek table
+    and (sums=True) one Adler-32 per 4 KiB block of the original. Every reader of plain files reads it."""
+    lib = load()
+    arr, p = _buf(data)
+    n = arr.size
+    need = ctypes.c_uint64()
+    check(lib.hz_encoded_size(p, n, ctypes.byref(need)), "hz_encoded_size")
+    flags = _seekable_flags(sums)
+    out = np.empty(need.value + lib.hz_seekable_trailer_bytes(need.value, n, flags), dtype=np.uint8)
+    got = ctypes.c_uint64()
+    check(lib.hz_encode_host_seekable(p, n, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(got), flags),
+          "hz_encode_host_seekable")
+    return out[:got.value].tobytes()
+
+
+def archive_seekable(path, out_path=None, chunk_bytes=1 << 30, sums=True, verbose=False):
+    """Streaming archive of path into a seekable file (default: path + ".compressed"): archive_stream()'s
+    bytes, then the trailer. Returns the output's name."""
+    out_path = str(path) + ".compressed" if out_path is None else out_path
+    check(load().hz_archive_stream_seekable(os.fsencode(path), os.fsencode(out_path), chunk_bytes, int(verbose),
+                                            _seekable_flags(sums)), "hz_archive_stream_seekable")
+    return str(out_path)
+
+
+def seekable_info(path_or_bytes):
+    """The trailer of a file (a path) or an image (bytes): a dict of hz_seekable_info's fields, or None
+    for a plain file. A trailer whose fields do not fit raises HZ_EFORMAT."""
+    lib = load()
+    info = _lib.SeekableInfo()
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        check(lib.hz_seekable_info_file(os.fsencode(path_or_bytes), ctypes.byref(info)), "hz_seekable_info_file")
+    else:
+        arr, _ = _buf(path_or_bytes)
+        last = np.ascontiguousarray(arr[-64:]) if arr.size >= 64 else None
+        check(lib.hz_seekable_footer_parse(None if last is None else last.ctypes.data_as(ctypes.c_void_p), arr.size,
+                                           ctypes.byref(info)), "hz_seekable_footer_parse")
+    return info.as_dict() if info.present else None
+
+
+def _load_trailer(path, want_sums):
+    lib = load()
+    info = seekable_info(path)
+    if info is None:
+        raise _lib.HZError(-5, "hz_seekable_load_file")
+    if want_sums and not info["flags"] & _lib.HZ_SEEKABLE_SUMS:
+        return None
+    seek, buf = _seek_table(info["nsym"])
+    sums = np.zeros(max(info["nblocks"], 1), dtype=np.uint32)
+    nsym = ctypes.c_uint64()
+    check(lib.hz_seekable_load_file(os.fsencode(path), buf.ctypes.data_as(ctypes.c_void_p), buf.size * 8,
+                                    sums.ctypes.data_as(ctypes.c_void_p) if want_sums else None, sums.size * 4,
+                                    ctypes.byref(nsym)), "hz_seekable_load_file")
+    return sums[:info["nblocks"]] if want_sums else seek
+
+
+def load_seek(path):
+    """The seek table (uint64) stored in a seekable file's trailer; a plain file raises HZ_EFORMAT."""
+    return _load_trailer(path, False)
+
+
+def load_sums(path):
+    """The block sums (uint32) stored in a seekable file's trailer, or None when it was written without."""
+    return _load_trailer(path, True)
+
+
+def read_seekable(path_or_bytes, ranges, verify=False):
+    """[(offset, length), ...] byte ranges of the original from a seekable file (a path: only the footer,
+    the header, the table words and payload bytes of the ranges are read) or image (bytes), the table
+    taken from its trailer: a list of bytes, in the ranges' order. verify=True checks every decoded block
+    against its stored sum; a mismatch raises HZError(HZ_ECHECKSUM) with .block the smallest bad block."""
+    lib = load()
+    offs, cnts, out = _byte_ranges(ranges)
+    flags = _lib.HZ_SEEKABLE_VERIFY if verify else 0
+    bad = ctypes.c_uint64()
+    tail = (offs.ctypes.data_as(ctypes.c_void_p), cnts.ctypes.data_as(ctypes.c_void_p), offs.size,
+            out.ctypes.data_as(ctypes.c_void_p), flags, ctypes.byref(bad))
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        rc, name = lib.hz_seekable_read_file(os.fsencode(path_or_bytes), *tail), "hz_seekable_read_file"
+    else:
+        arr, p = _buf(path_or_bytes)
+        rc, name = lib.hz_seekable_read_host(p, arr.size, *tail), "hz_seekable_read_host"
+    if rc == _lib.HZ_ECHECKSUM:
+        raise _lib.HZError(rc, name, block=bad.value)
+    check(rc, name)
+    return _split(out, cnts)
+
+
+def verify_seekable(path):
+    """Decode the whole of a seekable file and check every block against its stored sum (nothing is
+    kept). Raises HZError(HZ_ECHECKSUM) with .block the first bad block."""
+    bad = ctypes.c_uint64()
+    rc = load().hz_seekable_verify_file(os.fsencode(path), ctypes.byref(bad))
+    if rc == _lib.HZ_ECHECKSUM:
+        raise _lib.HZError(rc, "hz_seekable_verify_file", block=bad.value)
+    check(rc, "hz_seekable_verify_file")
+
+
 class Device:
     """Stage API on device pointers (ints), stream-ordered on one HIP stream."""
 
@@ -360,6 +475,11 @@ class Device:
 
     def hist16(self, d_in, n, d_hist, accumulate=False):
         check(self.lib.hz_hist16(self.h, d_in, n, d_hist, int(accumulate)), "hz_hist16")
+
+    def block_sums(self, d_in, n, d_sums):
+        """One Adler-32 per 4096 bytes of d_in[0..n) (16-byte aligned), the last block zero-extended, into
+        d_sums (block_sums_bytes(n) bytes): hz_block_sums."""
+        check(self.lib.hz_block_sums(self.h, d_in, n, d_sums), "hz_block_sums")
 
     def codebook_build(self, d_hist, d_cb):
         """Device codebook: d_hist (u64 x 65536) -> d_cb (sizeof(Codebook) bytes)."""

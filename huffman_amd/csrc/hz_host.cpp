@@ -27,6 +27,7 @@ extern "C" const char* hz_strerror(int st) {
         case HZ_EIO: return "file I/O error";
         case HZ_ENODEV: return "no usable gfx950 device";
         case HZ_ENOENT: return "input file does not exist";
+        case HZ_ECHECKSUM: return "decoded block does not match its checksum";
         default: return "unknown error";
     }
 }
@@ -170,6 +171,19 @@ extern "C" int hz_hist16(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t* d
     return timed_stage(c, HZ_STAGE_HIST, "launch_hist16", [&] {
         return launch_hist16(d_in, n, reinterpret_cast<unsigned long long*>(d_hist), c->ncu, c->stream);
     }, false);  // (the kernel reports no errors)
+}
+
+extern "C" uint64_t hz_block_sums_bytes(uint64_t n) {
+    return 4 * (n / HZ_SUM_BLOCK_BYTES + (n % HZ_SUM_BLOCK_BYTES ? 1 : 0));
+}
+
+extern "C" int hz_block_sums(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint32_t* d_sums) {
+    if (!c) return HZ_EINVAL;
+    if (n == 0) return HZ_OK;
+    if (!d_in || !d_sums || (((uintptr_t)d_in) & 15) || (((uintptr_t)d_sums) & 3)) return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    const hipError_t e = launch_block_sums(d_in, n, d_sums, c->ncu, c->stream);  // (the kernel reports no errors)
+    return e == hipSuccess ? HZ_OK : hz_hip_fail(e, "launch_block_sums", __FILE_NAME__, __LINE__);
 }
 
 extern "C" uint64_t hz_ranges_bytes(uint64_t n) { return range_geom(n / 2).bytes; }

@@ -10,6 +10,7 @@
 
 #include "hz_file_io.h"
 #include "hz_host.h"
+#include "hz_seekable.h"
 #include "hz_stream_plan.h"
 
 using namespace hz;
@@ -44,7 +45,9 @@ int plan_encode(const uint8_t* in, uint64_t n, hz_ctx** ctx, DevBuf& din, Encode
 // Encode a host buffer into a complete .compressed image. seek (nullable): the image's seek table from the
 // writer (hz_pack_seek), hz_seek_bytes(n / 2) bytes: the pack's output starts at the file byte of the first
 // payload bit, which is where the table's bits count from.
-int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint32_t* nsym_out, uint64_t* seek = nullptr) {
+// sums (nullable): hz_block_sums' words of the input's 2 * (n / 2) symbol bytes, while it is on the device.
+int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint32_t* nsym_out, uint64_t* seek = nullptr,
+                 std::vector<uint32_t>* sums = nullptr) {
     hz_ctx* c;
     DevBuf din;
     EncodePlan p;
@@ -67,7 +70,7 @@ int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint3
         const uint64_t start_bit = pend_bits;
         const uint64_t pay_bytes = file_bytes - hbytes_full;
         const uint64_t words = (start_bit + p.payload_bits + 31) / 32;
-        DevBuf dout, dseek;
+        DevBuf dout, dseek, dsums;
         if ((rc = dout.alloc(words * 4))) return rc;
         const uint32_t lead = (uint32_t)(pend >> (8 - pend_bits)) * (pend_bits ? 1 : 0);
         if (seek) {
@@ -80,6 +83,13 @@ int encode_image(const uint8_t* in, uint64_t n, std::vector<uint8_t>& out, uint3
         if (rc) return rc;
         HZ_TRY(hipMemcpyAsync(out.data() + hbytes_full, dout.p, pay_bytes, hipMemcpyDeviceToHost, c->stream));
         if (seek) HZ_TRY(hipMemcpyAsync(seek, dseek.p, hz_seek_bytes(nsym), hipMemcpyDeviceToHost, c->stream));
+        if (sums) {
+            const uint64_t sums_bytes = hz_block_sums_bytes(2 * nsym);
+            sums->resize(sums_bytes / 4);
+            if ((rc = dsums.alloc(sums_bytes))) return rc;
+            if ((rc = hz_block_sums(c, (const uint8_t*)din.p, 2 * nsym, (uint32_t*)dsums.p))) return rc;
+            HZ_TRY(hipMemcpyAsync(sums->data(), dsums.p, sums_bytes, hipMemcpyDeviceToHost, c->stream));
+        }
         if ((rc = hz_ctx_sync(c))) return rc;
     } else if (pend_bits) {
         out[hbytes_full] = pend;  // unreachable (header is byte aligned without symbols) but kept exact
@@ -100,27 +110,45 @@ struct OpenedImage {
     mutable std::vector<uint8_t> span;
     std::unique_ptr<hz_codebook> cb{new hz_codebook()};
     hz_header_info info;
+    hz_seekable_info si;  // the file's trailer (present = 0: a plain file); the image ends where it begins
     uint64_t nsym = 0;  // symbols
-    uint64_t pay = 0;   // payload bytes: from info.payload_byte to the end of the file
+    uint64_t pay = 0;   // payload bytes: from info.payload_byte to the end of the image
 
     int open(const uint8_t* file, uint64_t len) {
-        const int rc = hz_header_parse(file, len, cb.get(), &info);
+        uint64_t end;
+        int rc = image_end(file, len, &end, &si);
         if (rc) return rc;
+        if ((rc = hz_header_parse(file, end, cb.get(), &info))) return rc;
+        if (info.payload_byte > end || (si.present && si.n != info.n)) return HZ_EFORMAT;
         f = file;
         nsym = info.n / 2;
-        pay = len - info.payload_byte;
+        pay = end - info.payload_byte;
         return HZ_OK;
     }
     int open_file(const char* path) {
         int rc = file.open(path);
         if (rc) return rc;
-        const uint64_t fsize = file.size();
+        uint64_t fsize;
+        if ((rc = image_end_fd(file.fd(), file.size(), &fsize, &si))) return rc;
         head.resize(std::min<uint64_t>(fsize, kMaxHeaderBytes));
         if ((rc = read_at(head.data(), head.size(), 0))) return rc;
         if ((rc = hz_header_parse(head.data(), head.size(), cb.get(), &info))) return rc;
-        if (info.payload_byte > fsize) return HZ_EFORMAT;
+        if (info.payload_byte > fsize || (si.present && si.n != info.n)) return HZ_EFORMAT;
         nsym = info.n / 2;
         pay = fsize - info.payload_byte;
+        return HZ_OK;
+    }
+    // trailer words (si.present): seek entries [first, first + count), the sums of blocks [first, first + count)
+    int seek_words(uint64_t* dst, uint64_t first, uint64_t count) const {
+        return bytes_at((uint8_t*)dst, 8 * count, si.seek_off + 8 * first);
+    }
+    int sum_words(uint32_t* dst, uint64_t first, uint64_t count) const {
+        return bytes_at((uint8_t*)dst, 4 * count, si.sums_off + 4 * first);
+    }
+    // file bytes [off, off + n): from memory, or read from the file (these bytes and no others)
+    int bytes_at(uint8_t* dst, uint64_t n, uint64_t off) const {
+        if (!f) return read_at(dst, n, off);
+        memcpy(dst, f + off, n);
         return HZ_OK;
     }
     // on the calling thread whatever the size (parallel piece reads are open: DESIGN.md section 10, item 6)
@@ -335,6 +363,43 @@ int decode_ranges_image(const uint8_t* f, uint64_t len, const uint64_t* seek, co
     return HZ_OK;
 }
 
+// One gathered batch on the device: one copy each of buffer, compact table, pieces and ranges up, one
+// hz_decode_ranges_pieces into a device temporary of tmp.size() bytes, one copy back, one sync.
+// sums (nullable; tmp.size() a multiple of 4096): the temporary is zero-filled first, and
+// hz_block_sums' words of what the decode left there come back with it.
+int run_gathered(const OpenedImage& im, const std::vector<uint8_t>& buf, const std::vector<uint64_t>& words,
+                 const hz_piece* pieces, uint32_t np, const hz_piece_range* prg, uint32_t nranges,
+                 std::vector<uint8_t>& tmp, std::vector<uint32_t>* sums) {
+    int rc;
+    hz_ctx* c;
+    if ((rc = default_ctx(&c))) return rc;
+    HZ_TRY(hipSetDevice(c->device));
+    if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
+    DevBuf dbuf, dseek, dpc, drg, dout, dsums;
+    const uint64_t buf_bytes = buf.size(), seek_words = words.size(), tmp_bytes = tmp.size();
+    const uint64_t pc_bytes = sizeof(hz_piece) * (uint64_t)np, rg_bytes = sizeof(hz_piece_range) * (uint64_t)nranges;
+    if ((rc = dbuf.alloc(buf_bytes)) || (rc = dseek.alloc(8 * seek_words)) || (rc = dpc.alloc(pc_bytes)) ||
+        (rc = drg.alloc(rg_bytes)) || (rc = dout.alloc(tmp_bytes)))
+        return rc;
+    HZ_TRY(hipMemcpyAsync(dbuf.p, buf.data(), buf_bytes, hipMemcpyHostToDevice, c->stream));
+    HZ_TRY(hipMemcpyAsync(dseek.p, words.data(), 8 * seek_words, hipMemcpyHostToDevice, c->stream));
+    HZ_TRY(hipMemcpyAsync(dpc.p, pieces, pc_bytes, hipMemcpyHostToDevice, c->stream));
+    HZ_TRY(hipMemcpyAsync(drg.p, prg, rg_bytes, hipMemcpyHostToDevice, c->stream));
+    if (sums) HZ_TRY(hipMemsetAsync(dout.p, 0, tmp_bytes, c->stream));
+    if ((rc = hz_decode_ranges_pieces(c, (const uint8_t*)dbuf.p, buf_bytes, (const uint64_t*)dseek.p, seek_words,
+                                      (const hz_piece*)dpc.p, np, im.nsym, (const hz_piece_range*)drg.p, nranges,
+                                      (uint8_t*)dout.p, tmp_bytes, nullptr, 0)))
+        return rc;
+    if (sums) {
+        sums->resize(hz_block_sums_bytes(tmp_bytes) / 4);
+        if ((rc = dsums.alloc(hz_block_sums_bytes(tmp_bytes)))) return rc;
+        if ((rc = hz_block_sums(c, (const uint8_t*)dout.p, tmp_bytes, (uint32_t*)dsums.p))) return rc;
+        HZ_TRY(hipMemcpyAsync(sums->data(), dsums.p, hz_block_sums_bytes(tmp_bytes), hipMemcpyDeviceToHost, c->stream));
+    }
+    HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
+    return hz_ctx_sync(c);  // the host buffers of the copies live until here
+}
+
 // The same bytes from gathered pieces, of an image in memory or a file on disk: hz_seek_pieces' plan,
 // one zeroed host buffer with each piece copied (or read) into its place, the compact table, one copy
 // each of buffer, table, pieces and ranges to the device, one hz_decode_ranges_pieces, one copy back,
@@ -366,27 +431,122 @@ int decode_ranges_pieces_opened(const OpenedImage& im, const uint64_t* seek, con
             else if ((rc = im.read_at(buf.data() + p.buf_byte, p.bytes, im.info.payload_byte + p.stream_byte))) return rc;
             std::copy(seek + p.first_block, seek + p.first_block + p.nblocks + 1, words.begin() + p.seek_index);
         }
-        hz_ctx* c;
-        if ((rc = default_ctx(&c))) return rc;
-        HZ_TRY(hipSetDevice(c->device));
-        if ((rc = hz_codebook_upload_decode(c, im.cb.get()))) return rc;
-        DevBuf dbuf, dseek, dpc, drg, dout;
-        const uint64_t pc_bytes = sizeof(hz_piece) * (uint64_t)np, rg_bytes = sizeof(hz_piece_range) * (uint64_t)nranges;
-        if ((rc = dbuf.alloc(buf_bytes)) || (rc = dseek.alloc(8 * seek_words)) || (rc = dpc.alloc(pc_bytes)) ||
-            (rc = drg.alloc(rg_bytes)) || (rc = dout.alloc(tmp_bytes)))
-            return rc;
-        HZ_TRY(hipMemcpyAsync(dbuf.p, buf.data(), buf_bytes, hipMemcpyHostToDevice, c->stream));
-        HZ_TRY(hipMemcpyAsync(dseek.p, words.data(), 8 * seek_words, hipMemcpyHostToDevice, c->stream));
-        HZ_TRY(hipMemcpyAsync(dpc.p, pieces.data(), pc_bytes, hipMemcpyHostToDevice, c->stream));
-        HZ_TRY(hipMemcpyAsync(drg.p, prg.data(), rg_bytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = hz_decode_ranges_pieces(c, (const uint8_t*)dbuf.p, buf_bytes, (const uint64_t*)dseek.p, seek_words,
-                                          (const hz_piece*)dpc.p, np, im.nsym, (const hz_piece_range*)drg.p, nranges,
-                                          (uint8_t*)dout.p, tmp_bytes, nullptr, 0)))
-            return rc;
-        HZ_TRY(hipMemcpyAsync(tmp.data(), dout.p, tmp_bytes, hipMemcpyDeviceToHost, c->stream));
-        if ((rc = hz_ctx_sync(c))) return rc;  // the host buffers of the four copies live until here
+        if ((rc = run_gathered(im, buf, words, pieces.data(), np, prg.data(), nranges, tmp, nullptr))) return rc;
     }
     give_byte_ranges(im, rg, tmp, offsets, counts, nranges, out);
+    return HZ_OK;
+}
+
+// ---- seekable files: ranges through the trailer (include/huffman_amd.h "seekable files") ----
+
+// The seek words a read holds of a table that stays in the file: one run per range, its entries b0 .. b1 + 1.
+struct SeekRuns {
+    struct Run {
+        uint64_t first;
+        std::vector<uint64_t> w;
+    };
+    std::vector<Run> runs;
+    const Run* find(uint64_t first, uint64_t count) const {
+        for (const Run& r : runs)
+            if (r.first <= first && first + count <= r.first + r.w.size()) return &r;
+        return nullptr;
+    }
+    // (seek_pieces_by asks only for words the runs hold: entries b0 and b1 + 1 of the ranges they were read for)
+    static uint64_t word(const void* arg, uint64_t i) {
+        const Run* r = static_cast<const SeekRuns*>(arg)->find(i, 1);
+        return r ? r->w[i - r->first] : UINT64_MAX;
+    }
+};
+
+// Byte ranges of the original of an opened image with a trailer, the table read from it: per range its
+// words b0 .. b1 + 1 (all hz_seek_span reads), the plan from those, then each piece's words and bytes.
+// verify: every range rounded out to whole blocks, each at a 4096-aligned place of a zero-filled
+// temporary, the temporary's block sums compared with the file's. discard: nothing is given to `out`.
+int seekable_read_opened(const OpenedImage& im, const uint64_t* offsets, const uint64_t* counts, uint32_t nranges,
+                         uint8_t* out, uint32_t flags, uint64_t* bad_block, bool discard = false) {
+    int rc;
+    if (!im.si.present) return HZ_EFORMAT;
+    if (flags & ~HZ_SEEKABLE_VERIFY) return HZ_EINVAL;
+    const bool verify = (flags & HZ_SEEKABLE_VERIFY) != 0;
+    if (verify && !(im.si.flags & HZ_SEEKABLE_SUMS)) return HZ_EINVAL;
+    if (nranges == 0) return HZ_OK;
+    if (!offsets || !counts) return HZ_EINVAL;
+    std::vector<hz_range> rg;  // the covering symbols of every range, where give_byte_ranges finds them
+    uint64_t tmp_bytes, total;
+    if ((rc = byte_ranges(im, offsets, counts, nranges, rg, &tmp_bytes, &total))) return rc;
+    if (total && !out && !discard) return HZ_EINVAL;
+    std::vector<hz_range> dec = rg;  // what the device decodes: the same, or the blocks around them
+    if (verify) {
+        tmp_bytes = 0;
+        for (uint32_t i = 0; i < nranges; ++i) {
+            if (!rg[i].sym_count) continue;
+            const uint64_t s0 = rg[i].sym_begin / kBlockSyms * kBlockSyms;
+            const uint64_t s1 = std::min(index_blocks(rg[i].sym_begin + rg[i].sym_count) * kBlockSyms, im.nsym);
+            dec[i] = hz_range{s0, s1 - s0, tmp_bytes};
+            rg[i].out_byte = tmp_bytes + 2 * (rg[i].sym_begin - s0);
+            tmp_bytes += index_blocks(s1 - s0) * HZ_SUM_BLOCK_BYTES;
+        }
+    }
+    std::vector<uint8_t> tmp(tmp_bytes);
+    if (tmp_bytes) {
+        SeekRuns held;
+        for (uint32_t i = 0; i < nranges; ++i) {
+            if (!dec[i].sym_count) continue;
+            const uint64_t b0 = dec[i].sym_begin / kBlockSyms, b1 = (dec[i].sym_begin + dec[i].sym_count - 1) / kBlockSyms;
+            if (held.find(b0, b1 - b0 + 2)) continue;
+            held.runs.push_back({b0, std::vector<uint64_t>(b1 - b0 + 2)});
+            if ((rc = im.seek_words(held.runs.back().w.data(), b0, b1 - b0 + 2))) return rc;
+        }
+        std::vector<hz_piece> pieces(nranges);
+        std::vector<hz_piece_range> prg(nranges);
+        uint32_t np;
+        uint64_t buf_bytes, seek_words;
+        if ((rc = seek_pieces_by(SeekRuns::word, &held, im.nsym, im.pay, dec.data(), nranges, pieces.data(), &np, prg.data(),
+                                 &buf_bytes, &seek_words)))
+            return rc;
+        std::vector<uint8_t> buf(buf_bytes, 0);
+        std::vector<uint64_t> words(seek_words);
+        for (uint32_t k = 0; k < np; ++k) {
+            const hz_piece& p = pieces[k];
+            if ((rc = im.bytes_at(buf.data() + p.buf_byte, p.bytes, im.info.payload_byte + p.stream_byte))) return rc;
+            // a piece's words: held already when one range spans it, else read (the hull of several ranges)
+            if (const SeekRuns::Run* r = held.find(p.first_block, p.nblocks + 1))
+                std::copy_n(r->w.begin() + (p.first_block - r->first), p.nblocks + 1, words.begin() + p.seek_index);
+            else if ((rc = im.seek_words(words.data() + p.seek_index, p.first_block, p.nblocks + 1)))
+                return rc;
+        }
+        std::vector<uint32_t> got;
+        if ((rc = run_gathered(im, buf, words, pieces.data(), np, prg.data(), nranges, tmp, verify ? &got : nullptr))) return rc;
+        if (verify) {
+            uint64_t bad = UINT64_MAX;
+            std::vector<uint32_t> want;
+            for (uint32_t i = 0; i < nranges; ++i) {
+                if (!dec[i].sym_count) continue;
+                const uint64_t b0 = dec[i].sym_begin / kBlockSyms, nb = index_blocks(dec[i].sym_count);
+                want.resize(nb);
+                if ((rc = im.sum_words(want.data(), b0, nb))) return rc;
+                for (uint64_t k = 0; k < nb; ++k)
+                    if (want[k] != got[dec[i].out_byte / HZ_SUM_BLOCK_BYTES + k]) bad = std::min(bad, b0 + k);
+            }
+            if (bad != UINT64_MAX) {
+                if (bad_block) *bad_block = bad;
+                return HZ_ECHECKSUM;
+            }
+        }
+    }
+    if (!discard) give_byte_ranges(im, rg, tmp, offsets, counts, nranges, out);
+    return HZ_OK;
+}
+
+// hz_seekable_verify_file: the verified read over the whole original, a tile of output at a time.
+int seekable_verify_opened(const OpenedImage& im, uint64_t* bad_block) {
+    if (!im.si.present) return HZ_EFORMAT;
+    if (!(im.si.flags & HZ_SEEKABLE_SUMS)) return HZ_EINVAL;
+    constexpr uint64_t kTile = 64ull << 20;
+    for (uint64_t off = 0; off < im.info.n; off += kTile) {
+        const uint64_t cnt = std::min(kTile, im.info.n - off);
+        if (int rc = seekable_read_opened(im, &off, &cnt, 1, nullptr, HZ_SEEKABLE_VERIFY, bad_block, true)) return rc;
+    }
     return HZ_OK;
 }
 
@@ -484,5 +644,52 @@ extern "C" int hz_decode_range_file(const char* path, const uint64_t* seek, uint
         OpenedImage im;
         const int rc = im.open_file(path);
         return rc ? rc : decode_range_opened(im, seek, offset, count, out);
+    });
+}
+
+extern "C" int hz_encode_host_seekable(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len,
+                                       uint32_t flags) {
+    if ((!in && n) || !out_len || (flags & ~HZ_SEEKABLE_SUMS)) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        std::vector<uint8_t> img;
+        std::vector<uint64_t> seek(hz_seek_bytes(n / 2) / 8);
+        std::vector<uint32_t> sums;
+        int rc = encode_image(in, n, img, nullptr, seek.data(), flags & HZ_SEEKABLE_SUMS ? &sums : nullptr);
+        if (rc) return rc;
+        const uint64_t image_bytes = img.size();
+        uint64_t len = hz_seekable_trailer_bytes(image_bytes, n, flags);
+        if (!len) return HZ_EINVAL;
+        img.resize(image_bytes + len);
+        rc = hz_seekable_trailer_write(image_bytes, n, seek.data(), sums.data(), flags, img.data() + image_bytes, len, &len);
+        return rc ? rc : give(img, out, cap, out_len);
+    });
+}
+
+extern "C" int hz_seekable_read_host(const uint8_t* file, uint64_t len, const uint64_t* offsets, const uint64_t* counts,
+                                     uint32_t nranges, uint8_t* out, uint32_t flags, uint64_t* bad_block) {
+    if (!file) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open(file, len);
+        return rc ? rc : seekable_read_opened(im, offsets, counts, nranges, out, flags, bad_block);
+    });
+}
+
+extern "C" int hz_seekable_read_file(const char* path, const uint64_t* offsets, const uint64_t* counts, uint32_t nranges,
+                                     uint8_t* out, uint32_t flags, uint64_t* bad_block) {
+    if (!path) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open_file(path);
+        return rc ? rc : seekable_read_opened(im, offsets, counts, nranges, out, flags, bad_block);
+    });
+}
+
+extern "C" int hz_seekable_verify_file(const char* path, uint64_t* bad_block) {
+    if (!path) return HZ_EINVAL;
+    return guarded([&]() -> int {
+        OpenedImage im;
+        const int rc = im.open_file(path);
+        return rc ? rc : seekable_verify_opened(im, bad_block);
     });
 }

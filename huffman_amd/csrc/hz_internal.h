@@ -1,5 +1,5 @@
 // hz_internal.h -- shared layout constants, the table plan and launch interfaces between the host side
-// (hz_host.cpp, hz_image.cpp, hz_stream.cpp, hz_codebook.cpp) and the gfx950 kernels (hz_hist.hip, hz_pack.hip,
+// (hz_host.cpp, hz_image.cpp, hz_stream.cpp, hz_codebook.cpp) and the gfx950 kernels (hz_hist.hip, hz_sums.hip, hz_pack.hip,
 // hz_decode.hip, hz_ranges.hip, hz_index.hip, hz_chain.hip, hz_codebook_gpu.hip; DESIGN.md "Source layout").
 #pragma once
 #include <hip/hip_runtime.h>
@@ -310,6 +310,9 @@ hipError_t launch_hist16(const uint8_t* d_in, uint64_t n, unsigned long long* d_
                          hipStream_t s);
 hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long long* d_hist, void* d_ranges,
                                 uint32_t* d_err, hipStream_t s);  // range plan (RangeGeom)
+// ---- hz_sums.hip ------------------------------------------------------------
+// d_sums[i] = Adler-32 of d_in's bytes [4096 i, 4096 (i + 1)), bytes at or past n as zeros (d_in 16-byte aligned)
+hipError_t launch_block_sums(const uint8_t* d_in, uint64_t n, uint32_t* d_sums, int ncu, hipStream_t s);
 // ---- hz_pack.hip (and ensure_lds_limit, launch_scan: hz_device.h) -------------
 // d_ranges (nullable): the range plan of d_in from launch_hist16_ranges; *used_ranges = 1 when the
 // pack took it (else count + scan + write)
@@ -338,6 +341,15 @@ hipError_t launch_decode(const Tables& t, const uint8_t* d_payload, uint64_t pay
 // Random access (DESIGN.md "Random access"). d_seek: the stream's start[] (a full index when full_index);
 // d_payload holds the stream's payload bytes [base, base + payload_bytes); d_scratch: range_scratch_words().
 constexpr uint64_t kRangeLeadBytes = HZ_RANGE_LEAD_BYTES, kRangeTailBytes = HZ_RANGE_TAIL_BYTES;
+// hz_seek_span / hz_seek_pieces (hz_seek_plan.cpp) with the table behind an accessor: word(arg, i) is entry i,
+// asked for entries b0 and b1 + 1 of each non-empty range only, so a caller that holds just those words of a
+// table on disk (a seekable file's trailer) plans from them. arg must not be null.
+typedef uint64_t (*SeekWordFn)(const void* arg, uint64_t i);
+int seek_span_by(SeekWordFn word, const void* arg, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                 uint64_t* byte_begin, uint64_t* byte_end);
+int seek_pieces_by(SeekWordFn word, const void* arg, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges,
+                   uint32_t nranges, hz_piece* pieces, uint32_t* npieces, hz_piece_range* out, uint64_t* buf_bytes,
+                   uint64_t* seek_words);
 uint64_t range_scratch_words(uint64_t sym_begin, uint64_t sym_count);
 hipError_t launch_decode_range(const Tables& t, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t base,
                                const unsigned long long* d_seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,

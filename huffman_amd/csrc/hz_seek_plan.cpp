@@ -13,15 +13,22 @@
 
 using namespace hz;
 
-extern "C" int hz_seek_span(const uint64_t* seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
-                            uint64_t* byte_begin, uint64_t* byte_end) {
+namespace {
+
+uint64_t table_word(const void* seek, uint64_t i) { return static_cast<const uint64_t*>(seek)[i]; }
+
+}  // namespace
+
+int hz::seek_span_by(SeekWordFn word, const void* arg, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                     uint64_t* byte_begin, uint64_t* byte_end) {
     if (!byte_begin || !byte_end) return HZ_EINVAL;
     if (sym_begin > nsym || sym_count > nsym - sym_begin) return HZ_EINVAL;
     *byte_begin = *byte_end = 0;
     if (sym_count == 0) return HZ_OK;
-    if (!seek) return HZ_EINVAL;
+    if (!arg) return HZ_EINVAL;
     const uint64_t b0 = sym_begin / kBlockSyms, b1 = (sym_begin + sym_count - 1) / kBlockSyms;
-    const uint64_t first = seek[b0] / 8, last = seek[b1 + 1] / 8 + (seek[b1 + 1] % 8 ? 1 : 0);
+    const uint64_t w0 = word(arg, b0), w1 = word(arg, b1 + 1);
+    const uint64_t first = w0 / 8, last = w1 / 8 + (w1 % 8 ? 1 : 0);
     if (last < first) return HZ_EINVAL;
     // the staging window of a block starts 16 bytes below the 16-byte chunk of its first bit
     // (dec_stage_prefetch / dec_stage_commit; the walk's reader starts at that chunk, br_init) and
@@ -29,6 +36,11 @@ extern "C" int hz_seek_span(const uint64_t* seek, uint64_t nsym, uint64_t sym_be
     *byte_begin = first > kRangeLeadBytes ? (first - kRangeLeadBytes) & ~15ull : 0;
     *byte_end = last + kRangeTailBytes;
     return HZ_OK;
+}
+
+extern "C" int hz_seek_span(const uint64_t* seek, uint64_t nsym, uint64_t sym_begin, uint64_t sym_count,
+                            uint64_t* byte_begin, uint64_t* byte_end) {
+    return seek_span_by(table_word, seek, nsym, sym_begin, sym_count, byte_begin, byte_end);
 }
 
 namespace {
@@ -39,7 +51,7 @@ struct Span {
     uint32_t range;
 };
 
-int seek_pieces(const uint64_t* seek, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges, uint32_t nranges,
+int seek_pieces(SeekWordFn word, const void* arg, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges, uint32_t nranges,
                 hz_piece* pieces, uint32_t* npieces, hz_piece_range* out, uint64_t* buf_bytes, uint64_t* seek_words) {
     std::vector<Span> spans;
     spans.reserve(nranges);
@@ -49,7 +61,7 @@ int seek_pieces(const uint64_t* seek, uint64_t nsym, uint64_t payload_bytes, con
         out[i].out_byte = ranges[i].out_byte;
         out[i].piece = 0;
         Span s;
-        const int rc = hz_seek_span(seek, nsym, ranges[i].sym_begin, ranges[i].sym_count, &s.begin, &s.end);
+        const int rc = seek_span_by(word, arg, nsym, ranges[i].sym_begin, ranges[i].sym_count, &s.begin, &s.end);
         if (rc) return rc;
         if (ranges[i].sym_count == 0) continue;
         if (s.begin >= payload_bytes) return HZ_EFORMAT;
@@ -97,17 +109,24 @@ int seek_pieces(const uint64_t* seek, uint64_t nsym, uint64_t payload_bytes, con
 
 }  // namespace
 
-extern "C" int hz_seek_pieces(const uint64_t* seek, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges,
-                              uint32_t nranges, hz_piece* pieces, uint32_t* npieces, hz_piece_range* out,
-                              uint64_t* buf_bytes, uint64_t* seek_words) {
+int hz::seek_pieces_by(SeekWordFn word, const void* arg, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges,
+                       uint32_t nranges, hz_piece* pieces, uint32_t* npieces, hz_piece_range* out, uint64_t* buf_bytes,
+                       uint64_t* seek_words) {
     if (!npieces || !buf_bytes || !seek_words) return HZ_EINVAL;
     *npieces = 0;
     *buf_bytes = *seek_words = 0;
     if (nranges == 0) return HZ_OK;
     if (!ranges || !pieces || !out) return HZ_EINVAL;
     try {
-        return seek_pieces(seek, nsym, payload_bytes, ranges, nranges, pieces, npieces, out, buf_bytes, seek_words);
+        return seek_pieces(word, arg, nsym, payload_bytes, ranges, nranges, pieces, npieces, out, buf_bytes, seek_words);
     } catch (const std::bad_alloc&) {
         return HZ_ENOMEM;
     }
+}
+
+extern "C" int hz_seek_pieces(const uint64_t* seek, uint64_t nsym, uint64_t payload_bytes, const hz_range* ranges,
+                              uint32_t nranges, hz_piece* pieces, uint32_t* npieces, hz_piece_range* out,
+                              uint64_t* buf_bytes, uint64_t* seek_words) {
+    return seek_pieces_by(table_word, seek, nsym, payload_bytes, ranges, nranges, pieces, npieces, out, buf_bytes,
+                          seek_words);
 }

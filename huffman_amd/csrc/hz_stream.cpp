@@ -17,6 +17,7 @@
 
 #include "hz_file_io.h"
 #include "hz_host.h"
+#include "hz_seekable.h"
 #include "hz_stream_plan.h"
 
 using namespace hz;
@@ -181,6 +182,11 @@ int table_out(Spans& spans, hz_ctx* c, const SeekSink* sink, const DevBuf& dseek
 // writer (the pack's output starts at the file byte of the first payload bit, which is where the table's
 // bits count from), into one device table copied out once at the end. Chunks are whole blocks, and a
 // chunk's end bit comes back from the table: no per-chunk block index.
+//
+// seekable >= 0 (hz_archive_stream_seekable, its flags): the flow is its own sink and puts the table behind
+// the image as a trailer (hz_seekable.h). With HZ_SEEKABLE_SUMS every chunk's hz_block_sums follows its pack
+// on the same device bytes: chunks are whole blocks, so chunk k's words stand at block off / 4096 of one
+// device array, copied out once at the end like the table.
 struct ArchiveFlow {
     const char* in_path;
     const char* out_path;
@@ -188,6 +194,7 @@ struct ArchiveFlow {
     int verbose;
     bool resident;
     const SeekSink* sink;
+    int seekable = -1;
 
     hz_ctx* c = nullptr;
     uint64_t n = 0, nsym_total = 0;
@@ -210,8 +217,12 @@ struct ArchiveFlow {
     FileReader fin{&g_timing};
     Spans spans;
     PinnedBuf hin[2], hout[2];
-    DevBuf din[2], dhist, dall, dcb, dhead, dinfo, dpay, dseek, dout[2], didx;
+    DevBuf din[2], dhist, dall, dcb, dhead, dinfo, dpay, dseek, dsums, dout[2], didx;
     std::vector<uint64_t> hist = std::vector<uint64_t>(HZ_NSYM);
+    std::vector<uint64_t> table;  // seekable: the trailer's table and sums, and the sink that fills the table
+    std::vector<uint32_t> sums;
+    uint64_t own_nsym = 0;
+    SeekSink own_sink{nullptr, 0, nullptr};
     std::unique_ptr<hz_codebook> cb{new hz_codebook()};
     std::vector<uint8_t> head;
     uint64_t dinfo_h[4] = {0, 0, 0, 0};
@@ -231,6 +242,9 @@ struct ArchiveFlow {
         return on;
     }
 
+    bool with_sums() const { return seekable >= 0 && ((uint32_t)seekable & HZ_SEEKABLE_SUMS); }
+    uint64_t image_bytes() const { return (hbits + pbits + 7) / 8; }
+
     int open_and_size() {
         if (!in_path || !out_path || chunk_bytes < 64) return HZ_EINVAL;
         if (sink && !sink->nsym) return HZ_EINVAL;
@@ -238,6 +252,13 @@ struct ArchiveFlow {
         if (rc) return rc;
         n = fin.size();
         nsym_total = n / 2;
+        if (seekable >= 0) {
+            if ((uint32_t)seekable & ~HZ_SEEKABLE_SUMS) return HZ_EINVAL;
+            table.resize(hz_seek_bytes(nsym_total) / 8);
+            if (with_sums()) sums.resize(hz_block_sums_bytes(2 * nsym_total) / 4);
+            own_sink = SeekSink{table.data(), 8 * table.size(), &own_nsym};
+            sink = &own_sink;
+        }
         ch = ArchiveChunks(chunk_bytes, sink != nullptr, n);
         if (sink) {
             *sink->nsym = n / 2;
@@ -359,11 +380,13 @@ struct ArchiveFlow {
     int open_output() {
         int rc;
         if ((rc = fout.open(out_path))) return rc;
-        fout.reserve(hb + (pend_bits + pbits + 7) / 8);
+        fout.reserve(hb + (pend_bits + pbits + 7) / 8 +
+                     (seekable >= 0 ? hz_seekable_trailer_bytes(image_bytes(), n, (uint32_t)seekable) : 0));
         if ((rc = fout.write_now(head.data(), hb, 0))) return rc;
         written = hb;
         lead = pend_bits ? (uint32_t)(pend >> (8 - pend_bits)) : 0u;
         if (sink && nsym_total && (rc = dseek.alloc(hz_seek_bytes(nsym_total)))) return rc;
+        if (!sums.empty() && (rc = dsums.alloc(4 * sums.size()))) return rc;
         return HZ_OK;
     }
 
@@ -378,10 +401,13 @@ struct ArchiveFlow {
     // sink, the table's entries too (sym_base: the symbols before; bit_base: the payload bits before d_out).
     int pack_call(const void* d_in, uint64_t len, uint32_t start, void* d_out, uint64_t cap, uint64_t* d_index,
                   uint64_t sym_base, uint64_t bit_base) {
-        return spans.timed(c->stream, &g_timing.kernel_ms, [&] {
-            return sink ? hz_pack_seek(c, (const uint8_t*)d_in, len, start, lead, (uint8_t*)d_out, cap, nullptr, sym_base,
-                                       bit_base, nsym_total, (uint64_t*)dseek.p)
-                        : hz_pack(c, (const uint8_t*)d_in, len, start, lead, (uint8_t*)d_out, cap, d_index);
+        return spans.timed(c->stream, &g_timing.kernel_ms, [&]() -> int {
+            if (!sink) return hz_pack(c, (const uint8_t*)d_in, len, start, lead, (uint8_t*)d_out, cap, d_index);
+            const int rc = hz_pack_seek(c, (const uint8_t*)d_in, len, start, lead, (uint8_t*)d_out, cap, nullptr, sym_base,
+                                        bit_base, nsym_total, (uint64_t*)dseek.p);
+            if (rc || sums.empty()) return rc;
+            // the call's symbols begin a block (hz_pack_seek: sym_base is a multiple of 2048)
+            return hz_block_sums(c, (const uint8_t*)d_in, len & ~(uint64_t)1, (uint32_t*)dsums.p + sym_base / kBlockSyms);
         });
     }
 
@@ -498,6 +524,29 @@ struct ArchiveFlow {
         return HZ_OK;
     }
 
+    // The trailer behind the image, in hz_seekable_trailer_write's layout: the table and the sums leave from
+    // the vectors that hold them (no second copy of either), the padding and the footer around them.
+    int write_trailer() {
+        int rc;
+        if (!sums.empty()) {
+            rc = spans.copy(c->stream, &g_timing.d2h_ms, sums.data(), dsums.p, 4 * sums.size(), hipMemcpyDeviceToHost);
+            if (rc || (rc = hz_ctx_sync(c))) return rc;
+        }
+        if (written != image_bytes()) return HZ_EFORMAT;
+        const SeekableLayout l = seekable_layout(written, n, (uint32_t)seekable);
+        if (!l.ok || l.seek_bytes != 8 * table.size() || l.sums_bytes != 4 * sums.size()) return HZ_EINVAL;
+        const uint64_t sums_at = l.seek_off + l.seek_bytes, tail_off = sums_at + l.sums_bytes;
+        const uint64_t tail_len = l.file_bytes - tail_off;  // under 8 bytes of padding, then the footer
+        uint8_t pad[8] = {0}, tail[8 + HZ_SEEKABLE_FOOTER_BYTES] = {0};
+        if ((rc = seekable_footer(written, n, (uint32_t)seekable, tail + tail_len - HZ_SEEKABLE_FOOTER_BYTES))) return rc;
+        if ((rc = fout.write_now(pad, l.seek_off - written, written)) ||
+            (rc = fout.write_now((const uint8_t*)table.data(), l.seek_bytes, l.seek_off)) ||
+            (rc = fout.write_now((const uint8_t*)sums.data(), l.sums_bytes, sums_at)) ||
+            (rc = fout.write_now(tail, tail_len, tail_off)))
+            return rc;
+        return HZ_OK;
+    }
+
     int close_and_report() {
         if (int rc = fout.close()) return rc;
         spans.fold();
@@ -527,6 +576,7 @@ struct ArchiveFlow {
             if (!resident && (rc = pack_streamed())) return rc;
         }
         if ((rc = table_out(spans, c, sink, dseek, nsym_total))) return rc;
+        if (seekable >= 0 && (rc = write_trailer())) return rc;
         return close_and_report();
     }
 };
@@ -547,6 +597,12 @@ static int timed_call(F&& body) {
     const int rc = guarded(body);
     g_timing.total_ms = ms_since(t0);
     return rc;
+}
+
+extern "C" int hz_archive_stream_seekable(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
+                                          uint32_t flags) {
+    if (flags & ~HZ_SEEKABLE_SUMS) return HZ_EINVAL;
+    return timed_call([&] { return ArchiveFlow{in_path, out_path, chunk_bytes, verbose, false, nullptr, (int)flags}.run(); });
 }
 
 extern "C" int hz_archive_stream(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose) {
@@ -646,10 +702,13 @@ struct ExtractFlow {
         chunk_bytes &= ~(uint64_t)15;
         int rc = fin.open(in_path);
         if (rc) return rc;
-        fsize = fin.size();
+        // a file with a trailer (hz_seekable.h) ends where its image ends: the trailer is no payload
+        hz_seekable_info si;
+        if ((rc = image_end_fd(fin.fd(), fin.size(), &fsize, &si))) return rc;
         head.resize(std::min<uint64_t>(fsize, kMaxHeaderBytes));
         if ((rc = fin.read(head.data(), head.size(), 0))) return rc;
         if ((rc = parse_header_for_extract(head, cb.get(), &info))) return rc;
+        if (si.present && si.n != info.n) return HZ_EFORMAT;
         nsym = info.n / 2;
         if (sink) {
             *sink->nsym = nsym;

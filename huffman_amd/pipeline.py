@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .codec import Device, build_codebook, header_bits, index_bytes, payload_bits, seek_bytes, write_header
+from .codec import Device, block_sums_bytes, build_codebook, header_bits, index_bytes, payload_bits, seek_bytes, write_header
 
 
 class Plan:
@@ -88,6 +88,13 @@ class StreamCodec:
         self._ranges_of = None
 
     # -- stages ---------------------------------------------------------------
+    def block_sums(self, x):
+        """The block checksums of a uint8 device tensor (16-byte aligned): an int32 tensor holding the u32
+        words, one Adler-32 per 4096 bytes with the last block zero-extended (hz_block_sums)."""
+        sums = torch.empty(block_sums_bytes(x.numel()) // 4, dtype=torch.int32, device=self.device)
+        self.dev.block_sums(x.data_ptr(), x.numel(), sums.data_ptr())
+        return sums
+
     def histogram(self, x, accumulate=False):
         n = x.numel()
         # the range plan needs a 16-byte aligned input (hz_hist16_ranges); offset views take hz_hist16

@@ -41,7 +41,8 @@ enum {
     HZ_ETIMEOUT = -7,  /* a device-side wait exceeded its bound (reserved) */
     HZ_EIO = -8,       /* file I/O error */
     HZ_ENODEV = -9,    /* no usable gfx950 device */
-    HZ_ENOENT = -10    /* input file does not exist (the reference CLIs exit 0 on it) */
+    HZ_ENOENT = -10,   /* input file does not exist (the reference CLIs exit 0 on it) */
+    HZ_ECHECKSUM = -11 /* a decoded block does not match its stored checksum (seekable files) */
 };
 
 /* Codebook in the reference's order and bit conventions. */
@@ -100,6 +101,21 @@ int hz_ctx_sync(hz_ctx *ctx);
  * it and replay it on whatever d_in holds then.
  * Replaces calculateFrequency (Compressor.cu:38-48, launch :369-372). */
 int hz_hist16(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_hist, int accumulate);
+
+/* Block checksums of data on the device: word i of d_sums (hz_block_sums_bytes(n) = 4 * ceil(n / 4096)
+ * bytes) is the Adler-32 (RFC 1950, zlib's adler32) of bytes [4096 i, min(4096 (i + 1), n)) of d_in
+ * EXTENDED WITH ZERO BYTES TO 4096, so every sum is over exactly 4096 bytes and the last block is no
+ * special case: with d_k the block's bytes (0 past n), a = (1 + sum d_k) mod 65521, b = (4096 +
+ * sum (4096 - k) d_k) mod 65521, word = b << 16 | a. A block is one seek-table block of output
+ * (2 * hz_index_stride() bytes). One read pass: a wave per block, 1 KiB per wave-load.
+ * d_in must be 16-byte aligned (HZ_EINVAL otherwise; d_sums 4-byte aligned). Stream-ordered, no
+ * scratch and no host wait: a HIP graph can capture it and replay it on whatever d_in holds then.
+ * n == 0: HZ_OK, nothing launched. No load leaves [d_in, d_in + n) rounded up to a 4-byte word, and
+ * bytes of that word at or past n are masked, never summed. The reference has no counterpart (its
+ * format carries no checksum). */
+#define HZ_SUM_BLOCK_BYTES 4096
+uint64_t hz_block_sums_bytes(uint64_t n);
+int hz_block_sums(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_sums);
 
 /* Host codebook from a host histogram with the reference's semantics: thrust
  * stable sort (Compressor.cu:378-393,414,419-425) + GenerateCL / GenerateCW /
@@ -261,7 +277,8 @@ int hz_index_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes
  * stream's end bit; 8 bytes per 4 KiB of output. Bits count from byte 0 of the
  * stream's payload buffer, as in the index. To keep one: hz_pack (or
  * hz_index_build) into an index buffer, copy its first hz_seek_bytes(nsym)
- * bytes to the host and store them beside the stream. To read symbols back:
+ * bytes to the host and store them beside the stream, or in it: a seekable file
+ * carries its table in a trailer (below, "seekable files"). To read symbols back:
  * load the table, ask hz_seek_span which payload bytes the range needs, put
  * those bytes (or the whole payload) and the table on the device, upload the
  * codebook (hz_codebook_upload_decode) and call hz_decode_range. */
@@ -700,6 +717,119 @@ int hz_decode_ranges_host(const uint8_t *file, uint64_t len, const uint64_t *see
 int hz_seek_build_host(const uint8_t *file, uint64_t len, uint64_t *seek, uint64_t cap_bytes, uint64_t *nsym);
 int hz_decode_range_host(const uint8_t *file, uint64_t len, const uint64_t *seek, uint64_t offset,
                          uint64_t count, uint8_t *out);
+
+/* ---- seekable files: seek table and block checksums in a file trailer -------
+ * The reference `extract` reads the header, decodes N / 2 codewords and stops
+ * (Decompressor.cu:103-108,259-291): it never reads to the end of the file. Bytes
+ * behind the payload are invisible to it, so a SEEKABLE file is a .compressed file
+ * with a trailer, and stays a valid .compressed file for the reference and for every
+ * reader here:
+ *
+ *   [ the .compressed image, byte for byte what the plain writer produces ]  image_bytes
+ *   [ 0..7 zero bytes up to a multiple of 8 ]
+ *   [ seek table: u64 x (nblocks + 1), little-endian ]   at seek_off
+ *   [ block sums: u32 x nblocks ]                        at sums_off, only with HZ_SEEKABLE_SUMS
+ *   [ zero bytes up to a multiple of 8 ]
+ *   [ footer, 64 bytes, at the end of the file ]
+ *
+ * The seek table is the one hz_archive_stream_seek returns: bits count from the file
+ * byte that holds the first payload bit. Sum b is hz_block_sums' word of the original's
+ * bytes [4096 b, min(4096 (b + 1), 2 nsym)), zero-extended to 4096. The odd last byte
+ * of an odd-sized original lives in the header and is NOT covered by a sum.
+ * Footer, little-endian:
+ *    0  8 bytes magic "HZSKTRL1"
+ *    8  u32 version = 1
+ *   12  u32 flags (bit 0: sums present; other bits 0)
+ *   16  u64 n, the original's size in bytes
+ *   24  u64 image_bytes
+ *   32  u64 seek_off
+ *   40  u64 sums_off (0 when absent)
+ *   48  u32 block symbols = 2048
+ *   52  u32 0
+ *   56  u32 0
+ *   60  u32 Adler-32 of footer bytes [0, 60)
+ * A file HAS A TRAILER when the magic and the footer check both match; any other file
+ * is a plain file, which is not an error (present = 0). A file whose magic and check
+ * match but whose fields do not fit is HZ_EFORMAT; they fit when version = 1, no
+ * unknown flag bit is set, block symbols = 2048, seek_off is a multiple of 8 with
+ * image_bytes <= seek_off < image_bytes + 8, sums_off = seek_off + hz_seek_bytes(n / 2)
+ * when sums are present (0 when not), and the file's size is the end of the last
+ * section rounded up to 8, plus 64 -- all of it computed without a wrap, whatever n
+ * claims. Flows that also parse the header return HZ_EFORMAT when its N differs from
+ * the footer's. n < 2 still gets a trailer: an empty table, no sums words, the footer.
+ *
+ * EXISTING READERS IGNORE THE TRAILER: for hz_extract_stream, hz_extract_stream_seek,
+ * hz_extract_file, hz_decode_host, hz_seek_build_host, hz_decode_range_host,
+ * hz_decode_ranges_host, hz_decode_ranges_host_pieces, hz_decode_range_file and
+ * hz_decode_ranges_file (and the `extract` CLI) a file with a trailer ends at
+ * image_bytes; files without one take the path they always took.
+ *
+ * Host only, no device call (hz_seekable.cpp links without HIP):
+ *   hz_seekable_trailer_bytes: bytes of the trailer behind an image of image_bytes
+ *     (padding, table, sums with HZ_SEEKABLE_SUMS, padding, footer); 0 when they do not
+ *     fit 64 bits.
+ *   hz_seekable_trailer_write: those bytes into out (cap below them: HZ_ECAP with *len
+ *     set). seek / sums may be NULL when the table / the sums are empty.
+ *   hz_seekable_footer_parse: the last 64 bytes of a file of file_bytes (last64 may be
+ *     NULL when file_bytes < 64: a plain file) into info; nsym = n / 2, nblocks =
+ *     ceil(nsym / 2048).
+ *   hz_seekable_info_file: the same for a path (HZ_ENOENT for a missing file); reads
+ *     the footer only.
+ *   hz_seekable_load_file: the table (hz_seek_bytes(*nsym) bytes) and, with sums non-NULL,
+ *     the sums (4 * nblocks bytes) of a file with a trailer; a capacity too small:
+ *     HZ_ECAP with *nsym set; a plain file: HZ_EFORMAT; sums asked of a file without
+ *     them: HZ_EINVAL. */
+#define HZ_SEEKABLE_FOOTER_BYTES 64
+#define HZ_SEEKABLE_SUMS   1u   /* writers: store block sums */
+#define HZ_SEEKABLE_VERIFY 2u   /* readers: check every decoded block against its sum */
+typedef struct hz_seekable_info {
+    uint32_t present, version, flags, reserved;
+    uint64_t n, nsym, nblocks, image_bytes, seek_off, sums_off, file_bytes;
+} hz_seekable_info;
+uint64_t hz_seekable_trailer_bytes(uint64_t image_bytes, uint64_t n, uint32_t flags);
+int hz_seekable_trailer_write(uint64_t image_bytes, uint64_t n, const uint64_t *seek, const uint32_t *sums,
+                              uint32_t flags, uint8_t *out, uint64_t cap, uint64_t *len);
+int hz_seekable_footer_parse(const uint8_t *last64, uint64_t file_bytes, hz_seekable_info *info);
+int hz_seekable_info_file(const char *path, hz_seekable_info *info);
+int hz_seekable_load_file(const char *path, uint64_t *seek, uint64_t seek_cap_bytes,
+                          uint32_t *sums, uint64_t sums_cap_bytes, uint64_t *nsym);
+
+/* Writers (device work inside). The first image_bytes of the output are byte for byte
+ * what hz_encode_host / hz_archive_stream write for the same input; the table comes from
+ * the writer as in hz_encode_host_seek / hz_archive_stream_seek (no pass over the finished
+ * file), and with HZ_SEEKABLE_SUMS the sums from hz_block_sums on the input while it is on
+ * the device for the pack: chunk k writes its words at block (chunk offset / 4096) of one
+ * device array, copied out once at the end like the table. The streaming form's host
+ * memory is its chunks plus the table and the sums, and the output's final size, trailer
+ * included, is reserved before the first write. flags other than HZ_SEEKABLE_SUMS:
+ * HZ_EINVAL. hz_encode_host_seekable: cap too small gives HZ_ECAP with *out_len set. */
+int hz_encode_host_seekable(const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_len, uint32_t flags);
+int hz_archive_stream_seekable(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose, uint32_t flags);
+
+/* Readers. hz_seekable_read_host / hz_seekable_read_file: byte ranges of the original with
+ * the semantics of hz_decode_ranges_host_pieces / hz_decode_ranges_file (odd offsets and
+ * counts, the odd last byte from the header, list order, HZ_EINVAL past the original's
+ * size), with the table taken from the file's trailer; a file without one: HZ_EFORMAT.
+ * The file form reads the 64-byte footer, the header (at most 1 MiB), the seek words
+ * [first_block, first_block + nblocks] of each piece (pread at seek_off + 8 first_block;
+ * first each range's own words b0 .. b1 + 1, which is all hz_seek_span reads, then
+ * hz_seek_pieces on the words it has), each piece's payload bytes and, with
+ * HZ_SEEKABLE_VERIFY, the sums words of the blocks it decodes: never the whole table.
+ * flags = HZ_SEEKABLE_VERIFY: every range is rounded out to whole blocks (down to a
+ * multiple of 2048 symbols, up to the next one or nsym) and decoded, by the same single
+ * hz_decode_ranges_pieces call, into a zero-filled device temporary at a 4096-aligned
+ * offset; one hz_block_sums runs over the temporary and every block's word is compared
+ * with the file's (the zero fill makes the stream's last, partial block match). A
+ * mismatch: HZ_ECHECKSUM, *bad_block (nullable) the smallest failing block, out not
+ * written. HZ_SEEKABLE_VERIFY on a file without sums: HZ_EINVAL.
+ * hz_seekable_verify_file: the verified read over [0, n) in tiles of at most 64 MiB of
+ * output, the bytes discarded: HZ_OK, HZ_ECHECKSUM with the first bad block, or the
+ * decoder's own status. */
+int hz_seekable_read_host(const uint8_t *file, uint64_t len, const uint64_t *offsets, const uint64_t *counts,
+                          uint32_t nranges, uint8_t *out, uint32_t flags, uint64_t *bad_block);
+int hz_seekable_read_file(const char *path, const uint64_t *offsets, const uint64_t *counts,
+                          uint32_t nranges, uint8_t *out, uint32_t flags, uint64_t *bad_block);
+int hz_seekable_verify_file(const char *path, uint64_t *bad_block);
 
 #ifdef __cplusplus
 }
