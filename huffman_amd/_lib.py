@@ -21,6 +21,7 @@ HZ_SUM_BLOCK_BYTES = 4096   # one block checksum per seek-table block of output
 HZ_SEEKABLE_FOOTER_BYTES = 64
 HZ_SEEKABLE_SUMS = 1        # writers: store block sums
 HZ_SEEKABLE_VERIFY = 2      # readers: check every decoded block against its sum
+HZ_SEEKABLE_MIN_WINDOW = 16384  # hz_seekable_attach_file, hz_extract_stream_verified: the smallest window
 HZ_POS_LIMIT = (1 << 64) - 1 - 0xFFFF  # every stream position a base-taking call reaches stays below it
 
 STATUS = {
@@ -178,6 +179,9 @@ PROTOTYPES = [
     ("hz_seekable_read_host", _I, [_P, _U64, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U64)]),
     ("hz_seekable_read_file", _I, [ctypes.c_char_p, _P, _P, _U32, _P, _U32, ctypes.POINTER(_U64)]),
     ("hz_seekable_verify_file", _I, [ctypes.c_char_p, ctypes.POINTER(_U64)]),
+    ("hz_block_sums_check", _I, [_P, _P, _U64, _P, _U64, _P]),
+    ("hz_seekable_attach_file", _I, [ctypes.c_char_p, _U64, _U32, ctypes.POINTER(_I)]),
+    ("hz_extract_stream_verified", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I, ctypes.POINTER(_U64)]),
 ]
 
 _lib = None

@@ -446,6 +446,30 @@ def verify_seekable(path):
     check(rc, "hz_seekable_verify_file")
 
 
+def make_seekable(path, sums=True, window_bytes=256 << 20):
+    """Make an existing .compressed file seekable in place: the trailer archive_seekable() would have written
+    (the table from the index-less walk, with sums=True the block sums of the decoded rounds) is appended and
+    the image's bytes stay as they are; a trailer without sums gets them when sums=True. Returns True when a
+    trailer was written, False when the file already had what was asked for (hz_seekable_attach_file)."""
+    attached = ctypes.c_int()
+    check(load().hz_seekable_attach_file(os.fsencode(path), window_bytes, _seekable_flags(sums), ctypes.byref(attached)),
+          "hz_seekable_attach_file")
+    return bool(attached.value)
+
+
+def extract_verified(path, out_path=None, window_bytes=256 << 20, verbose=False):
+    """Streaming extract of a seekable file with sums, every block checked against its stored sum before it
+    is written (out_path=None: decode and check only). A mismatch raises HZError(HZ_ECHECKSUM) with .block
+    the smallest bad block; the output then holds the verified rounds before it
+    (hz_extract_stream_verified)."""
+    bad = ctypes.c_uint64()
+    rc = load().hz_extract_stream_verified(os.fsencode(path), None if out_path is None else os.fsencode(out_path),
+                                           window_bytes, int(verbose), ctypes.byref(bad))
+    if rc == _lib.HZ_ECHECKSUM:
+        raise _lib.HZError(rc, "hz_extract_stream_verified", block=bad.value)
+    check(rc, "hz_extract_stream_verified")
+
+
 class Device:
     """Stage API on device pointers (ints), stream-ordered on one HIP stream."""
 
@@ -480,6 +504,11 @@ class Device:
         """One Adler-32 per 4096 bytes of d_in[0..n) (16-byte aligned), the last block zero-extended, into
         d_sums (block_sums_bytes(n) bytes): hz_block_sums."""
         check(self.lib.hz_block_sums(self.h, d_in, n, d_sums), "hz_block_sums")
+
+    def block_sums_check(self, d_in, n, d_expect, block_base, d_bad):
+        """The same sums compared with the words at d_expect: the smallest block_base + i whose block differs
+        is folded (atomic minimum) into the u64 at d_bad, which the caller set (hz_block_sums_check)."""
+        check(self.lib.hz_block_sums_check(self.h, d_in, n, d_expect, block_base, d_bad), "hz_block_sums_check")
 
     def codebook_build(self, d_hist, d_cb):
         """Device codebook: d_hist (u64 x 65536) -> d_cb (sizeof(Codebook) bytes)."""

@@ -186,6 +186,18 @@ extern "C" int hz_block_sums(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint32_
     return e == hipSuccess ? HZ_OK : hz_hip_fail(e, "launch_block_sums", __FILE_NAME__, __LINE__);
 }
 
+extern "C" int hz_block_sums_check(hz_ctx* c, const uint8_t* d_in, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                   uint64_t* d_bad) {
+    if (!c) return HZ_EINVAL;
+    if (n == 0) return HZ_OK;
+    if (!d_in || !d_expect || !d_bad || (((uintptr_t)d_in) & 15) || (((uintptr_t)d_expect) & 3) || (((uintptr_t)d_bad) & 7))
+        return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    const hipError_t e = launch_block_sums_check(d_in, n, d_expect, block_base, reinterpret_cast<unsigned long long*>(d_bad),
+                                                 c->ncu, c->stream);  // (the kernel reports no errors)
+    return e == hipSuccess ? HZ_OK : hz_hip_fail(e, "launch_block_sums_check", __FILE_NAME__, __LINE__);
+}
+
 extern "C" uint64_t hz_ranges_bytes(uint64_t n) { return range_geom(n / 2).bytes; }
 
 extern "C" int hz_hist16_ranges(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t* d_hist, int accumulate,

@@ -313,6 +313,8 @@ hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long l
 // ---- hz_sums.hip ------------------------------------------------------------
 // d_sums[i] = Adler-32 of d_in's bytes [4096 i, 4096 (i + 1)), bytes at or past n as zeros (d_in 16-byte aligned)
 hipError_t launch_block_sums(const uint8_t* d_in, uint64_t n, uint32_t* d_sums, int ncu, hipStream_t s);
+hipError_t launch_block_sums_check(const uint8_t* d_in, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                   unsigned long long* d_bad, int ncu, hipStream_t s);
 // ---- hz_pack.hip (and ensure_lds_limit, launch_scan: hz_device.h) -------------
 // d_ranges (nullable): the range plan of d_in from launch_hist16_ranges; *used_ranges = 1 when the
 // pack took it (else count + scan + write)

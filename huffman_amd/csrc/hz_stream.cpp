@@ -2,11 +2,13 @@
 // Decompressor.cu:47-114), streamed through bounded host and device memory on the process-wide context.
 // Each flow is a struct with one function per step; its file I/O is hz_file_io.cpp and its chunk and
 // window arithmetic hz_stream_plan.h, both free of HIP calls.
+#include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
@@ -667,15 +669,33 @@ int parse_header_for_extract(const std::vector<uint8_t>& head, hz_codebook* cb, 
 // earlier rounds consumed, into one device table copied out once at the end. A round redone after an
 // overrun rewrites its entries, and later rounds overwrite what the overrun attempt wrote past its
 // window. Without an out_path (sink only) nothing is decoded, copied out or written.
+//
+// The seekable flows run the same rounds in whole blocks (ExtractWindow's whole_blocks), as their own sink,
+// so a round's output, while it is still in dout, begins at block done / 2048 of the file's block sums:
+//   kAttach (hz_seekable_attach_file)      the table and, with HZ_SEEKABLE_SUMS, one hz_block_sums per round
+//     into one device array copied out once at the end like the table; no pinned output, no file write.
+//     Without the flag nothing is decoded.
+//   kVerified (hz_extract_stream_verified)  the trailer's sums uploaded once, and one hz_block_sums_check per
+//     round into one device word that comes home with the round's end bit; a round's bytes leave for the
+//     file only after that word said the round matched. An overrun attempt's word is discarded (reset before
+//     the redo). After the last round the walk's table is compared with the stored one.
 struct ExtractFlow {
+    enum Mode { kExtract, kAttach, kVerified };
+
     const char* in_path;
     const char* out_path;
     uint64_t chunk_bytes;
     int verbose;
     const SeekSink* sink;
+    Mode mode = kExtract;
+    uint32_t want = 0;              // kAttach: the flags asked for
+    uint64_t* bad_block = nullptr;  // kVerified: out, the smallest failing block
 
     hz_ctx* c = nullptr;
     bool write = false;
+    bool decode = false;   // the rounds decode into dout (kExtract: the same as write)
+    bool has_all = false;  // kAttach: the file's trailer already holds what `want` asks for
+    hz_seekable_info si;
     uint64_t fsize = 0, nsym = 0;
     hz_header_info info;
     ExtractWindow w{0, 0, 0, 0, 0};
@@ -689,31 +709,62 @@ struct ExtractFlow {
     Spans spans;
     std::vector<uint8_t> head;
     std::unique_ptr<hz_codebook> cb{new hz_codebook()};
-    DevBuf dwin[2], didx, dout, dseek;
+    DevBuf dwin[2], didx, dout, dseek, dsums, dbad;
     PinnedBuf hin, hout[2];  // hout: a round's output leaves (parallel writes) beside the next round
     uint64_t end_bit = 0;
+    uint64_t bad = UINT64_MAX;     // kVerified: the device's bad-block word, home with end_bit
+    std::vector<uint64_t> table;   // the seekable flows: the walk's table and the sink that fills it,
+    std::vector<uint64_t> stored;  // kVerified: the trailer's table,
+    std::vector<uint32_t> sums;    // and the sums: kAttach's from the rounds, kVerified's from the trailer
+    uint64_t own_nsym = 0;
+    SeekSink own_sink{nullptr, 0, nullptr};
     FileWriter fout{&g_timing};
     DrainGuard drain;
 
+    bool with_sums() const { return mode == kAttach && (want & HZ_SEEKABLE_SUMS); }
+
     int open_and_parse() {
-        if (!in_path || (!out_path && !sink) || chunk_bytes < 4096) return HZ_EINVAL;
+        if (!in_path || (!out_path && !sink && mode == kExtract) || chunk_bytes < 4096) return HZ_EINVAL;
         if (sink && !sink->nsym) return HZ_EINVAL;
         write = out_path != nullptr;
         chunk_bytes &= ~(uint64_t)15;
         int rc = fin.open(in_path);
         if (rc) return rc;
         // a file with a trailer (hz_seekable.h) ends where its image ends: the trailer is no payload
-        hz_seekable_info si;
         if ((rc = image_end_fd(fin.fd(), fin.size(), &fsize, &si))) return rc;
+        if (mode == kVerified && !si.present) return HZ_EFORMAT;
+        if (mode == kVerified && !(si.flags & HZ_SEEKABLE_SUMS)) return HZ_EINVAL;
+        if (mode == kAttach && si.present && (si.flags & want) == want) {
+            has_all = true;
+            return HZ_OK;
+        }
         head.resize(std::min<uint64_t>(fsize, kMaxHeaderBytes));
         if ((rc = fin.read(head.data(), head.size(), 0))) return rc;
         if ((rc = parse_header_for_extract(head, cb.get(), &info))) return rc;
         if (si.present && si.n != info.n) return HZ_EFORMAT;
         nsym = info.n / 2;
+        if (mode != kExtract && (rc = own_table())) return rc;
         if (sink) {
             *sink->nsym = nsym;
             if (hz_seek_bytes(nsym) && (!sink->seek || sink->cap_bytes < hz_seek_bytes(nsym))) return HZ_ECAP;
         }
+        return HZ_OK;
+    }
+
+    // The seekable flows' own table, sized by what the file can hold, and kVerified's trailer words.
+    int own_table() {
+        const uint64_t pay_bytes = fsize > info.payload_byte ? fsize - info.payload_byte : 0;
+        // a header whose N overstates the payload must not size the table: the decode would reject it anyway
+        if (!payload_holds(pay_bytes, info.payload_bit, nsym, cb->min_len)) return HZ_EFORMAT;
+        table.resize(hz_seek_bytes(nsym) / 8);
+        own_sink = SeekSink{table.data(), 8 * table.size(), &own_nsym};
+        sink = &own_sink;
+        if (mode != kVerified) return HZ_OK;
+        stored.resize(table.size());
+        sums.resize(si.nblocks);  // (the footer's own sizes add up to the file's: hz_seekable_footer_parse)
+        int rc;
+        if (!stored.empty() && (rc = pread_all(fin.fd(), (uint8_t*)stored.data(), 8 * stored.size(), si.seek_off))) return rc;
+        if (!sums.empty() && (rc = pread_all(fin.fd(), (uint8_t*)sums.data(), 4 * sums.size(), si.sums_off))) return rc;
         return HZ_OK;
     }
 
@@ -735,18 +786,31 @@ struct ExtractFlow {
         const auto tu = Clock::now();
         if ((rc = hz_codebook_upload_decode(c, cb.get()))) return rc;
         g_timing.host_ms += ms_since(tu);
-        w = ExtractWindow(chunk_bytes, nsym, fsize > info.payload_byte ? fsize - info.payload_byte : 0, info.payload_bit,
-                          cb->max_len);
+        const uint64_t pay_bytes = fsize > info.payload_byte ? fsize - info.payload_byte : 0;
+        // (the seekable flows: no window larger than the payload, so a small file takes small buffers)
+        const uint64_t window = mode == kExtract ? chunk_bytes
+                                                 : std::min(chunk_bytes, std::max<uint64_t>((pay_bytes + 15) & ~(uint64_t)15,
+                                                                                            HZ_SEEKABLE_MIN_WINDOW));
+        w = ExtractWindow(window, nsym, pay_bytes, info.payload_bit, cb->max_len, mode != kExtract);
+        decode = write || with_sums() || mode == kVerified;
         const auto ta = Clock::now();
         for (int i = 0; i < 2; ++i)
             if ((rc = dwin[i].alloc(w.W + 16))) return rc;
         if ((rc = didx.alloc(16))) return rc;  // the round's end bit
-        if (write && (rc = dout.alloc(2 * w.sym_cap + 16))) return rc;
+        if (decode && (rc = dout.alloc(2 * w.sym_cap + 16))) return rc;
         if (sink && (rc = dseek.alloc(hz_seek_bytes(nsym)))) return rc;
+        if (with_sums()) sums.resize(hz_block_sums_bytes(2 * nsym) / 4);
+        if (mode != kExtract && (rc = dsums.alloc(4 * sums.size()))) return rc;
+        if (mode == kVerified && (rc = dbad.alloc(8))) return rc;
         if ((rc = hin.alloc(w.W))) return rc;
         for (int i = 0; i < 2; ++i)
             if (write && (rc = hout[i].alloc(2 * w.sym_cap))) return rc;
         g_timing.alloc_ms += ms_since(ta);
+        if (mode == kVerified) {
+            HZ_TRY(hipMemsetAsync(dbad.p, 0xFF, 8, c->stream));
+            if ((rc = spans.copy(c->stream, &g_timing.h2d_ms, dsums.p, sums.data(), 4 * sums.size(), hipMemcpyHostToDevice)))
+                return rc;
+        }
         read_off = info.payload_byte;
         const uint64_t r = w.first_fill();
         if ((rc = refill_read(r))) return rc;
@@ -776,9 +840,22 @@ struct ExtractFlow {
                                               (uint64_t*)didx.p);
         });
     }
+    // the round's blocks begin at block w.done / 2048 (whole-block rounds): their sums stored (kAttach with
+    // sums) or compared with the trailer's (kVerified), on the output while it is in dout
+    int sums_call() {
+        if (!with_sums() && mode != kVerified) return HZ_OK;
+        uint32_t* words = (uint32_t*)dsums.p + w.done / kBlockSyms;
+        return spans.timed(c->stream, &g_timing.kernel_ms, [&] {
+            return mode == kVerified ? hz_block_sums_check(c, (const uint8_t*)dout.p, 2 * k, words, w.done / kBlockSyms,
+                                                           (uint64_t*)dbad.p)
+                                     : hz_block_sums(c, (const uint8_t*)dout.p, 2 * k, words);
+        });
+    }
     int launch() {
-        if (int rc = decode_call()) return rc;
+        int rc;
+        if ((rc = decode_call()) || (rc = sums_call())) return rc;
         HZ_TRY(hipMemcpyAsync(&end_bit, didx.p, 8, hipMemcpyDeviceToHost, c->stream));
+        if (mode == kVerified) HZ_TRY(hipMemcpyAsync(&bad, dbad.p, 8, hipMemcpyDeviceToHost, c->stream));
         return HZ_OK;
     }
 
@@ -790,9 +867,15 @@ struct ExtractFlow {
         if ((rc = hz_ctx_sync(c))) return rc;
         if (w.overran(end_bit)) {
             k = w.redo_syms();
+            // what the attempt's sums said of symbols past the window is no verdict
+            if (mode == kVerified) HZ_TRY(hipMemsetAsync(dbad.p, 0xFF, 8, c->stream));
             if ((rc = launch()) || (rc = hz_ctx_sync(c))) return rc;
         }
         if (w.truncated(end_bit)) return HZ_EFORMAT;
+        if (mode == kVerified && bad != UINT64_MAX) {  // the rounds before this one are the verified prefix
+            if (bad_block) *bad_block = bad;
+            return HZ_ECHECKSUM;
+        }
         if (write && (rc = spans.copy(c->stream, &g_timing.d2h_ms, hout[ob].p, dout.p, 2 * k, hipMemcpyDeviceToHost))) return rc;
         const uint64_t kdone = k;
         const int nxt = cur ^ 1;
@@ -830,17 +913,57 @@ struct ExtractFlow {
         return HZ_OK;
     }
 
+    // kAttach: the rounds' sums to the host, once
+    int sums_out() {
+        if (!with_sums() || sums.empty()) return HZ_OK;
+        const int rc = spans.copy(c->stream, &g_timing.d2h_ms, sums.data(), dsums.p, 4 * sums.size(), hipMemcpyDeviceToHost);
+        return rc ? rc : hz_ctx_sync(c);
+    }
+
     int run() {
         int rc;
-        if ((rc = open_and_parse()) || (rc = open_output())) return rc;
+        if ((rc = open_and_parse()) || has_all || (rc = open_output())) return rc;
         if (nsym > 0) {
             if ((rc = first_window())) return rc;
             while (w.done < nsym)
                 if ((rc = round())) return rc;
-            if ((rc = fout.wait()) || (rc = table_out(spans, c, sink, dseek, nsym))) return rc;
+            if ((rc = fout.wait()) || (rc = table_out(spans, c, sink, dseek, nsym)) || (rc = sums_out())) return rc;
             spans.fold();
         }
         return odd_byte_and_close();
+    }
+
+    // kVerified: whatever ends the flow early, the output ends at the last verified round's last byte (never
+    // at its reserved size); and a complete output whose stored table is not the walk's is HZ_EFORMAT.
+    int run_verified() {
+        const int rc = run();
+        if (rc) {
+            (void)fout.wait();
+            (void)fout.close();
+            return rc;
+        }
+        return table == stored ? HZ_OK : HZ_EFORMAT;
+    }
+
+    // kAttach: the trailer behind the image, written once every round has succeeded: padding, table and sums
+    // first, the footer last (until it stands the file is a plain file, or still ends in its old footer's
+    // place). The image's bytes are never rewritten.
+    int run_attach(int* attached) {
+        int rc = run();
+        if (rc || has_all) return rc;
+        uint64_t len = hz_seekable_trailer_bytes(fsize, info.n, want);
+        if (!len) return HZ_EINVAL;
+        std::vector<uint8_t> tr(len);
+        if ((rc = hz_seekable_trailer_write(fsize, info.n, table.data(), sums.data(), want, tr.data(), len, &len))) return rc;
+        const int fd = ::open(in_path, O_WRONLY);
+        if (fd < 0) return HZ_EIO;
+        const uint64_t body = len - HZ_SEEKABLE_FOOTER_BYTES;
+        rc = pwrite_all(fd, tr.data(), body, fsize);
+        if (!rc && ::ftruncate(fd, (off_t)(fsize + len)) != 0) rc = HZ_EIO;
+        if (!rc) rc = pwrite_all(fd, tr.data() + body, HZ_SEEKABLE_FOOTER_BYTES, fsize + body);
+        if (::close(fd) != 0 && !rc) rc = HZ_EIO;
+        if (!rc && attached) *attached = 1;
+        return rc;
     }
 };
 
@@ -855,6 +978,22 @@ extern "C" int hz_extract_stream_seek(const char* in_path, const char* out_path,
     if (!in_path || !nsym || chunk_bytes < 4096) return HZ_EINVAL;
     const SeekSink sink{seek, cap_bytes, nsym};
     return timed_call([&] { return ExtractFlow{in_path, out_path, chunk_bytes, verbose, &sink}.run(); });
+}
+
+extern "C" int hz_seekable_attach_file(const char* path, uint64_t chunk_bytes, uint32_t flags, int* attached) {
+    if (attached) *attached = 0;
+    if (!path || (flags & ~HZ_SEEKABLE_SUMS) || chunk_bytes < HZ_SEEKABLE_MIN_WINDOW) return HZ_EINVAL;
+    return timed_call([&] {
+        return ExtractFlow{path, nullptr, chunk_bytes, 0, nullptr, ExtractFlow::kAttach, flags}.run_attach(attached);
+    });
+}
+
+extern "C" int hz_extract_stream_verified(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,
+                                          uint64_t* bad_block) {
+    if (!in_path || chunk_bytes < HZ_SEEKABLE_MIN_WINDOW) return HZ_EINVAL;
+    return timed_call([&] {
+        return ExtractFlow{in_path, out_path, chunk_bytes, verbose, nullptr, ExtractFlow::kVerified, 0, bad_block}.run_verified();
+    });
 }
 
 extern "C" int hz_archive_stream_seek(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,

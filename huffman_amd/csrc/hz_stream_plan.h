@@ -41,11 +41,19 @@ struct ExtractWindow {
     uint64_t done = 0;      // symbols decoded by the rounds before this one
     uint64_t consumed = 0;  // payload bytes before the window (the seek entries' bit base)
     uint64_t file_left;     // payload bytes not yet read
+    bool whole_blocks;      // every round but the file's last is a positive multiple of kPlanBlockSyms
 
-    ExtractWindow(uint64_t window, uint64_t nsym_, uint64_t pay_total, uint32_t payload_bit, uint32_t cb_max_len)
+    // whole_blocks: each round's output then starts on a block of the seek table and of the block sums
+    // (hz_seekable_attach_file, hz_extract_stream_verified), on the redo path too: sym_cap is whole blocks,
+    // an estimate below one block becomes one block (it may overrun and be redone) and the redo bound is
+    // rounded down to blocks. The window must hold a block at max_len (HZ_SEEKABLE_MIN_WINDOW).
+    ExtractWindow(uint64_t window, uint64_t nsym_, uint64_t pay_total, uint32_t payload_bit, uint32_t cb_max_len,
+                  bool whole_blocks_ = false)
         : W(window), nsym(nsym_), max_len(std::max<uint32_t>(cb_max_len, 1)),
-          sym_cap(std::max<uint64_t>(W / 2, kPlanBlockSyms)), bit(payload_bit), file_left(pay_total) {
+          sym_cap(std::max<uint64_t>(W / 2, kPlanBlockSyms)), bit(payload_bit), file_left(pay_total),
+          whole_blocks(whole_blocks_) {
         mean = pay_total ? ((double)pay_total * 8 - payload_bit) / (double)nsym : (double)max_len;
+        if (whole_blocks) sym_cap = sym_cap / kPlanBlockSyms * kPlanBlockSyms;
     }
     // bytes of the first read: they fill the window from its front
     uint64_t first_fill() {
@@ -60,13 +68,21 @@ struct ExtractWindow {
         if (file_left == 0) return std::min(left, sym_cap);
         uint64_t k = (uint64_t)((double)avail / (mean * 1.03));
         k = std::min(std::min(left, sym_cap), k);
+        if (whole_blocks) return k < left ? std::min(left, whole(k)) : k;
         // whole blocks when the window holds at least one; a smaller window keeps k
         if (k < left && k >= kPlanBlockSyms) k = k / kPlanBlockSyms * kPlanBlockSyms;
         return std::max<uint64_t>(k, 1);
     }
     // the round's codes overran the window and the file has more: redo at the bound
     bool overran(uint64_t end_bit) const { return end_bit > have * 8 && file_left > 0; }
-    uint64_t redo_syms() const { return std::max<uint64_t>((have * 8 - bit) / max_len, 1); }
+    uint64_t redo_syms() const {
+        const uint64_t k = (have * 8 - bit) / max_len;
+        // (the overrun round asked for no more than min(left, sym_cap), and the bound's codes surely fit)
+        if (whole_blocks) return std::min(std::min(nsym - done, sym_cap), whole(k));
+        return std::max<uint64_t>(k, 1);
+    }
+    // k rounded down to blocks, one block at the least
+    static uint64_t whole(uint64_t k) { return std::max(k / kPlanBlockSyms * kPlanBlockSyms, kPlanBlockSyms); }
     // (after the redo) the codes end past all the file has: a truncated file
     bool truncated(uint64_t end_bit) const { return end_bit > have * 8; }
 

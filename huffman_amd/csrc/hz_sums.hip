@@ -1,6 +1,7 @@
 // hz_sums.hip -- block checksums of data on the device (the seekable trailer's sums, hz_seekable.h).
 //
-//   k_block_sums   one Adler-32 (RFC 1950) per 4096 bytes, the last block zero-extended
+//   k_block_sums        one Adler-32 (RFC 1950) per 4096 bytes, the last block zero-extended
+//   k_block_sums_check  the same words compared with expected ones: the smallest block that differs
 //
 // The reference has no counterpart: its format carries no checksum.
 #include "hz_device.h"
@@ -46,38 +47,67 @@ HZ_DEV void sums_add16(const uint4& v, uint32_t o, uint32_t& s1, uint32_t& s2) {
     s2 += (kSumBlockBytes - o) * s - p;
 }
 
-// One wave per block, grid-stride over the blocks. Lane l reads at 16 l + 1024 j of its block, j = 0..3:
-// a wave-load is 1 KiB contiguous. 4096 + s2 <= 4096 + 255 * 4096 * 4097 / 2 < 2^32, and every lane's
-// share is non-negative, so 32-bit sums need no reduction before the end.
+// One block's word, uniform over its wave. Lane l reads at 16 l + 1024 j of the block, j = 0..3: a wave-load
+// is 1 KiB contiguous. 4096 + s2 <= 4096 + 255 * 4096 * 4097 / 2 < 2^32, and every lane's share is
+// non-negative, so 32-bit sums need no reduction before the end.
+HZ_DEV uint32_t sums_block(const uint8_t* __restrict__ in, uint64_t n, uint64_t b, uint32_t lane) {
+    const uint64_t base = b * kSumBlockBytes;
+    uint4 v[4];
+    if (base + kSumBlockBytes <= n) {  // wave-uniform: every block but the last partial one
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const uint4*>(in + base + 16u * lane + 1024u * j);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = sums_load16(in, base + 16u * lane + 1024u * j, n);
+    }
+    uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sums_add16(v[j], 16u * lane + 1024u * j, s1, s2);
+    s1 = readlane(wave_incl_sum(s1), 63);  // DPP sums; the wave's totals are uniform from here
+    s2 = readlane(wave_incl_sum(s2), 63);
+    return ((kSumBlockBytes + s2) % kAdlerMod) << 16 | (1u + s1) % kAdlerMod;
+}
+
+// One wave per block, grid-stride over the blocks.
 __global__ __launch_bounds__(kSumThreads) void k_block_sums(const uint8_t* __restrict__ in, uint64_t n,
                                                            uint64_t nblocks, uint32_t* __restrict__ sums) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t step = (uint64_t)gridDim.x * (kSumThreads / kWave);
     for (uint64_t b = (uint64_t)blockIdx.x * (kSumThreads / kWave) + wave_id(); b < nblocks; b += step) {
-        const uint64_t base = b * kSumBlockBytes;
-        uint4 v[4];
-        if (base + kSumBlockBytes <= n) {  // wave-uniform: every block but the last partial one
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = *reinterpret_cast<const uint4*>(in + base + 16u * lane + 1024u * j);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = sums_load16(in, base + 16u * lane + 1024u * j, n);
-        }
-        uint32_t s1 = 0, s2 = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) sums_add16(v[j], 16u * lane + 1024u * j, s1, s2);
-        s1 = readlane(wave_incl_sum(s1), 63);  // DPP sums; the wave's totals are uniform from here
-        s2 = readlane(wave_incl_sum(s2), 63);
-        if (lane == 0u) sums[b] = ((kSumBlockBytes + s2) % kAdlerMod) << 16 | (1u + s1) % kAdlerMod;
+        const uint32_t word = sums_block(in, n, b, lane);
+        if (lane == 0u) sums[b] = word;
     }
 }
+
+// The same pass with nothing stored: block b's word against expect[b], and the smallest block_base + b that
+// differs folded into *bad (the caller's, never initialised here: calls accumulate into one word).
+__global__ __launch_bounds__(kSumThreads) void k_block_sums_check(const uint8_t* __restrict__ in, uint64_t n,
+                                                                 uint64_t nblocks, const uint32_t* __restrict__ expect,
+                                                                 uint64_t block_base, unsigned long long* __restrict__ bad) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t step = (uint64_t)gridDim.x * (kSumThreads / kWave);
+    for (uint64_t b = (uint64_t)blockIdx.x * (kSumThreads / kWave) + wave_id(); b < nblocks; b += step) {
+        const uint32_t word = sums_block(in, n, b, lane);
+        if (lane == 0u && word != expect[b]) atomicMin(bad, (unsigned long long)(block_base + b));
+    }
+}
+
+// eight workgroups (32 waves, 128 KiB of loads in flight) per CU, the rest by the grid stride
+static unsigned sums_grid(uint64_t nblocks, int ncu) { return (unsigned)grid_clamp((nblocks + 3) / 4, (uint64_t)ncu * 8); }
 
 hipError_t launch_block_sums(const uint8_t* d_in, uint64_t n, uint32_t* d_sums, int ncu, hipStream_t s) {
     if (n == 0) return hipSuccess;
     const uint64_t nblocks = (n + kSumBlockBytes - 1) / kSumBlockBytes;
-    // eight workgroups (32 waves, 128 KiB of loads in flight) per CU, the rest by the grid stride
-    const unsigned grid = (unsigned)grid_clamp((nblocks + 3) / 4, (uint64_t)ncu * 8);
-    hipLaunchKernelGGL(k_block_sums, dim3(grid), dim3(kSumThreads), 0, s, d_in, n, nblocks, d_sums);
+    hipLaunchKernelGGL(k_block_sums, dim3(sums_grid(nblocks, ncu)), dim3(kSumThreads), 0, s, d_in, n, nblocks, d_sums);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_sums_check(const uint8_t* d_in, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                   unsigned long long* d_bad, int ncu, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t nblocks = (n + kSumBlockBytes - 1) / kSumBlockBytes;
+    hipLaunchKernelGGL(k_block_sums_check, dim3(sums_grid(nblocks, ncu)), dim3(kSumThreads), 0, s, d_in, n, nblocks, d_expect,
+                       block_base, d_bad);
     return hipGetLastError();
 }
 

@@ -95,6 +95,13 @@ class StreamCodec:
         self.dev.block_sums(x.data_ptr(), x.numel(), sums.data_ptr())
         return sums
 
+    def block_sums_check(self, x, expect, bad, block_base=0):
+        """Compare the block checksums of a uint8 device tensor (16-byte aligned) with `expect` (int32, one
+        word per block): the smallest block_base + i that differs is folded into bad[0] (int64 holding a
+        u64; set it to -1, all ones, first). Nothing else is written (hz_block_sums_check)."""
+        assert expect.numel() * 4 >= block_sums_bytes(x.numel()) and expect.element_size() == 4
+        self.dev.block_sums_check(x.data_ptr(), x.numel(), expect.data_ptr(), block_base, bad.data_ptr())
+
     def histogram(self, x, accumulate=False):
         n = x.numel()
         # the range plan needs a 16-byte aligned input (hz_hist16_ranges); offset views take hz_hist16

@@ -117,6 +117,18 @@ int hz_hist16(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t *d_hist, in
 uint64_t hz_block_sums_bytes(uint64_t n);
 int hz_block_sums(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_sums);
 
+/* The same pass with nothing stored: block i's word is compared with d_expect[i] (4 * ceil(n / 4096)
+ * bytes, 4-byte aligned), and only a block that differs does a 64-bit atomic minimum of block_base + i
+ * into *d_bad (8-byte aligned). *d_bad is the caller's: the call never initialises it, so several
+ * calls (the rounds of hz_extract_stream_verified, each at its block_base) fold into one word; write
+ * UINT64_MAX first, and the word is then the smallest failing block or still UINT64_MAX. Alignment of
+ * d_in, bounds, grid shape, stream order and capturability are hz_block_sums' (the same loads and the
+ * same arithmetic: one per-block body in hz_sums.hip). No scratch, and the context's error word is
+ * not touched. n == 0: HZ_OK, nothing launched. HZ_EINVAL: a null pointer, d_in not 16-byte aligned,
+ * d_expect not 4-byte aligned, d_bad not 8-byte aligned. */
+int hz_block_sums_check(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, const uint32_t *d_expect,
+                        uint64_t block_base, uint64_t *d_bad);
+
 /* Host codebook from a host histogram with the reference's semantics: thrust
  * stable sort (Compressor.cu:378-393,414,419-425) + GenerateCL / GenerateCW /
  * toCpu (gpuHuffmanConstruction.h:353-494,551-579). U == 1 gets code "0"
@@ -830,6 +842,49 @@ int hz_seekable_read_host(const uint8_t *file, uint64_t len, const uint64_t *off
 int hz_seekable_read_file(const char *path, const uint64_t *offsets, const uint64_t *counts,
                           uint32_t nranges, uint8_t *out, uint32_t flags, uint64_t *bad_block);
 int hz_seekable_verify_file(const char *path, uint64_t *bad_block);
+
+/* Existing files, in place, and the verified whole-file read. Both are the windowed index-less
+ * extract (hz_extract_stream_seek: a payload window of chunk_bytes, the walk's own table collected) run
+ * in ROUNDS OF WHOLE BLOCKS: every round but the file's last decodes a positive multiple of 2048
+ * symbols, on the redo path too, so a round's output, while it is still on the device, begins at block
+ * (symbols done / 2048) of the file's block sums. A window must hold one block of the longest codes,
+ * 2048 x 56 bits = 14 336 bytes: chunk_bytes below HZ_SEEKABLE_MIN_WINDOW is HZ_EINVAL before anything
+ * is touched. A missing file: HZ_ENOENT before any device call.
+ *
+ * hz_seekable_attach_file: put a trailer behind a .compressed file that has none (the reference
+ * encoder's, hz_archive_stream's, the `archive` CLI's), or sums into a trailer written without them.
+ * flags is 0 or HZ_SEEKABLE_SUMS (anything else: HZ_EINVAL). With HZ_SEEKABLE_SUMS every round decodes
+ * into the device output buffer and one hz_block_sums over it writes the round's words into one device
+ * array, copied out once at the end like the table: no pinned output buffer, no file write. Without
+ * the flag nothing is decoded (hz_extract_stream_seek without an out_path). The trailer is composed by
+ * hz_seekable_trailer_write and appended once EVERY round has succeeded: padding, table and sums
+ * first, the footer last; bytes [0, image_bytes) are never rewritten. A truncated or malformed file
+ * returns its status (HZ_EFORMAT ...) and stays byte for byte what it was. A file that has a trailer
+ * with everything flags asks for: HZ_OK, *attached (nullable) = 0, the file untouched. One whose
+ * trailer lacks the sums asked for: the image ends at image_bytes and the new trailer is written from
+ * there over the old one (the file grows). Otherwise *attached = 1. Host memory: one pinned window,
+ * the table and the sums and the trailer composed from them, whatever the file's size. The result is
+ * what hz_archive_stream_seekable writes for the same original and flags when this library wrote the
+ * image, and for any valid image the file's bytes, the table hz_seek_build_host finds in them and
+ * hz_block_sums' words of the original.
+ *
+ * hz_extract_stream_verified: hz_extract_stream of a seekable file with sums, every block checked
+ * before it is written. A plain file: HZ_EFORMAT; a trailer without sums: HZ_EINVAL; a header N that
+ * differs from the footer's: HZ_EFORMAT. The stored table and sums are read from the trailer, the sums
+ * uploaded once; each round is hz_decode_indexless_seek and then hz_block_sums_check on its output at
+ * block_base = symbols done / 2048, into one device word (UINT64_MAX at first) that comes home with the
+ * round's end bit -- the one host wait a round already has. A round's bytes go to out_path only after
+ * the round matched. On a mismatch: HZ_ECHECKSUM, *bad_block (nullable) the smallest failing block,
+ * and the output ends after the rounds before the failing one: a verified prefix whose size is a
+ * multiple of 4096 (on any other failure too the output ends at its last written round, never at a
+ * reserved size). After the last round the table the walk produced is compared with the stored one
+ * on the host: HZ_EFORMAT when they differ -- the output is then complete and correct (every block
+ * matched), the status says the stored table is not this payload's, so range reads would fail.
+ * out_path NULL: decode and check, write nothing. */
+#define HZ_SEEKABLE_MIN_WINDOW 16384
+int hz_seekable_attach_file(const char *path, uint64_t chunk_bytes, uint32_t flags, int *attached);
+int hz_extract_stream_verified(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose,
+                               uint64_t *bad_block);
 
 #ifdef __cplusplus
 }
