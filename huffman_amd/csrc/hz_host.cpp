@@ -729,17 +729,25 @@ static int fixed_part_summary(hz_ctx* c, uint64_t* d_summary) {
 extern "C" int hz_indexless_scan(hz_ctx* c, const uint8_t* d_payload, uint64_t payload_bytes, uint64_t payload_bit_base,
                                  uint64_t start_bit, uint64_t nsym, uint64_t part_begin, uint64_t part_end,
                                  uint64_t entry_bit, uint64_t* d_summary) {
+    // (under 16 bytes the walk's 16-byte loads have no whole chunk to clamp to: such a view is refused)
     if (!c || !d_payload || part_end <= part_begin || payload_bytes < 16) return HZ_EINVAL;
     if (c->t.dec_mode < 0) return HZ_EINVAL;
+    if (payload_bit_base % 8) return HZ_EINVAL;  // the view begins on a byte of the stream
     if (start_bit > UINT64_MAX - part_end || !far_pos_ok(payload_bit_base, payload_bytes)) return HZ_EINVAL;
     // the view must hold the part, and the lead-in before it (the stream's bits from its start, when the
     // part begins less than HZ_INDEXLESS_LEAD_BITS into it)
     const uint64_t lead = part_begin < HZ_INDEXLESS_LEAD_BITS ? part_begin : HZ_INDEXLESS_LEAD_BITS;
     if (start_bit + part_begin - lead < payload_bit_base) return HZ_EINVAL;
     if (start_bit + part_end > payload_bit_base + payload_bytes * 8) return HZ_EINVAL;
+    // an explicit entry is a codeword start of this part: not before the part's first bit (a walk from
+    // there would count the previous part's codewords) and not below the view (FIXED16 decodes from
+    // entry - base)
+    const uint64_t floor = std::max(payload_bit_base, start_bit + part_begin);
+    if (entry_bit != UINT64_MAX && entry_bit < floor) return HZ_EINVAL;
     HZ_TRY(hipSetDevice(c->device));
     chain_invalidate(c->chain);
     c->fx.on = false;
+    c->part_floor = floor;
     if (c->t.dec_mode == DEC_FIXED16) {
         c->fx.payload = d_payload;
         c->fx.bytes = payload_bytes;
@@ -766,12 +774,14 @@ extern "C" int hz_indexless_scan(hz_ctx* c, const uint8_t* d_payload, uint64_t p
 
 extern "C" int hz_indexless_refix(hz_ctx* c, uint64_t entry_bit, uint64_t* d_summary) {
     if (c && c->fx.on) {
+        if (entry_bit < c->part_floor) return HZ_EINVAL;
         if (entry_bit < c->fx.start || (entry_bit - c->fx.start) % 16 || entry_bit > c->fx.xit) return HZ_EINVAL;
         HZ_TRY(hipSetDevice(c->device));
         c->fx.entry = entry_bit;
         return fixed_part_summary(c, d_summary);
     }
     if (!c || !chain_info(c->chain)) return HZ_EINVAL;
+    if (entry_bit != UINT64_MAX && entry_bit < c->part_floor) return HZ_EINVAL;  // (UINT64_MAX: the walked entry again)
     HZ_TRY(hipSetDevice(c->device));
     HZ_TRY(chain_refix(c->chain, c->t, entry_bit, c->ncu, c->stream));
     return part_summary(c, d_summary);
@@ -802,6 +812,8 @@ extern "C" int hz_indexless_seek(hz_ctx* c, uint64_t sym_base, uint64_t nsym, ui
     if (!c || !d_seek) return HZ_EINVAL;
     if (sym_base > stream_nsym || nsym > stream_nsym - sym_base) return HZ_EINVAL;
     unsigned long long* sk = reinterpret_cast<unsigned long long*>(d_seek);
+    if (!c->fx.on && !chain_info(c->chain)) return HZ_EINVAL;  // no pending part
+    if (nsym == 0) return HZ_OK;  // no codewords of the part: no entry is this call's
     if (c->fx.on) {  // stream bits throughout: the part's codeword S at entry + 16 S
         HZ_TRY(hipSetDevice(c->device));
         HZ_TRY(seek_fixed16(c->fx.entry, (c->fx.xit - c->fx.entry) / 16, c->fx.base + 8 * c->fx.bytes, sym_base, nsym,

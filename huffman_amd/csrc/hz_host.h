@@ -93,4 +93,7 @@ struct hz_ctx {
         const uint8_t* payload = nullptr;
         uint64_t bytes = 0, base = 0, start = 0, entry = 0, xit = 0;
     } fx;
+    // the least explicit entry bit of the pending part (chains or FIXED16): its first bit, start_bit +
+    // part_begin, which the view holds (hz_indexless_scan checks; hz_indexless_refix checks against this)
+    uint64_t part_floor = 0;
 };

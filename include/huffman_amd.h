@@ -526,7 +526,9 @@ int hz_decode_indexless(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_
  * HZ_EINVAL at the call: a null d_seek, sym_base + nsym > stream_nsym, no decode
  * tables, a non-null d_out that is not 16-byte aligned, no pending part,
  * bit_base + 8 * payload_bytes not below HZ_POS_LIMIT. nsym 0: HZ_OK, nothing
- * written. An invalid code reports HZ_EFORMAT at hz_ctx_sync. */
+ * written -- for hz_indexless_seek too (a part that holds no codeword start writes
+ * no entry, not even one that its entry bit would fill), where it still needs a
+ * pending part. An invalid code reports HZ_EFORMAT at hz_ctx_sync. */
 int hz_seek_build(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
                   uint64_t nsym, uint64_t *d_seek);
 int hz_decode_indexless_seek(hz_ctx *ctx, const uint8_t *d_payload, uint64_t payload_bytes, uint64_t start_bit,
@@ -574,24 +576,50 @@ int hz_pack_seek(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint64_t start_bi
  *       Bits are STREAM bits: bit 0 is bit 0 of the stream's payload buffer
  *       (the one hz_decode_indexless takes), and d_payload holds stream bits
  *       [payload_bit_base, payload_bit_base + 8 * payload_bytes) -- a rank may
- *       pass only its slice (payload_bit_base a multiple of 8). The slice must
+ *       pass only its slice. payload_bit_base is a multiple of 8 and
+ *       payload_bytes at least 16 (the walk loads 16-byte chunks), else
+ *       HZ_EINVAL. d_payload may have any byte alignment: the kernels view the
+ *       slice from the 64-byte line at or below d_payload to the 4-byte word
+ *       that holds its last byte (both inside the caller's allocation), no load
+ *       leaves that view, and what lies outside it reads as zeros. The slice must
  *       hold the part and the HZ_INDEXLESS_LEAD_BITS before it (or the stream
  *       from its start) and end below HZ_POS_LIMIT, else HZ_EINVAL; the part's
  *       last codeword may run up to max_len bits past part_end (missing bits
- *       read as zeros: keep them in the slice). nsym: the stream's symbols
+ *       read as zeros: keep them in the slice). An explicit entry_bit is a
+ *       codeword start of this part: below start_bit + part_begin (the part's
+ *       first bit, which the slice holds, so never below payload_bit_base) it is
+ *       HZ_EINVAL -- a walk from there would count the previous part's
+ *       codewords. part_end <= part_begin and a context without decode tables
+ *       are HZ_EINVAL too; every refusal is made at the call, with nothing
+ *       launched. nsym: the stream's symbols
  *       (sizes the part's record capacity from its mean bits per codeword;
  *       0 = unknown: the codebook's estimate).
  *   hz_indexless_refix : the part again from its true entry (the previous
  *       part's exit, when it differs from the walked entry); d_summary updated.
+ *       entry_bit obeys the scan's rule, against the pending part's first bit
+ *       (UINT64_MAX: its walked entry again), else HZ_EINVAL.
  *   hz_indexless_decode : the part's codewords into d_out (2 bytes each, from
  *       the part's first codeword), at most nsym of them (the stream's symbols
  *       from the part's first on); *d_end_bit as hz_decode_indexless when the
  *       stream's last codeword falls in this part (a stream bit).
  * The three calls keep their state in the context's scratch and point at its
  * decode tables: one part per context at a time, and any other call that uses
- * the scratch or the tables (hz_pack*, hz_index_build, hz_decode_indexless,
- * hz_codebook_upload_decode) ends the pending part -- hz_indexless_refix /
- * _decode then return HZ_EINVAL. The same holds for a HIP graph that captured
+ * the scratch or replaces the tables ends the pending part -- hz_indexless_refix /
+ * _decode / _seek then return HZ_EINVAL, whatever their nsym. (With a pending
+ * part and nsym != 0, hz_indexless_decode refuses a d_out that is null or not
+ * 16-byte aligned.) The calls that end a part are hz_pack,
+ * hz_pack_ranges, hz_pack_seek, hz_index_build, hz_decode_range, hz_decode_ranges,
+ * hz_decode_ranges_pieces, hz_codebook_upload_decode (and hz_codebook_upload), a
+ * further hz_indexless_scan (its part replaces the pending one) and, under every
+ * codebook but FIXED16, hz_decode_indexless, hz_decode_indexless_seek and
+ * hz_seek_build of a payload of at least 16 bytes. A call with nothing to do
+ * (no symbols, no ranges) returns before it touches the scratch. These use no
+ * scratch and leave a pending part good: hz_hist16, hz_block_sums(_check),
+ * hz_decode through a block index, hz_index_expand, hz_codebook_upload_encode,
+ * hz_codebook_build_device, hz_ctx_sync; under FIXED16 also hz_decode_indexless,
+ * hz_decode_indexless_seek and hz_seek_build (arithmetic positions, no walk),
+ * and under every codebook the serial decode of a payload under 16 bytes.
+ * The same holds for a HIP graph that captured
  * hz_decode_indexless: replay it only while no call on the context has grown
  * the scratch or replaced the decode tables since the capture.
  * Every codebook takes this path; a FIXED16 part (every code 16 bits) is
