@@ -22,7 +22,9 @@ HZ_SEEKABLE_FOOTER_BYTES = 64
 HZ_SEEKABLE_SUMS = 1        # writers: store block sums
 HZ_SEEKABLE_VERIFY = 2      # readers: check every decoded block against its sum
 HZ_SEEKABLE_MIN_WINDOW = 16384  # hz_seekable_attach_file, hz_extract_stream_verified: the smallest window
-HZ_POS_LIMIT = (1 << 64) - 1 - 0xFFFF  # every stream position a base-taking call reaches stays below it
+HZ_SUMS_ZERO_BAD = 1        # hz_block_sums_mark: overwrite a block that differs with zeros
+HZ_SALVAGE_KEEP_UNVERIFIED = 1  # hz_seekable_salvage_file: keep the decoded bytes of blocks that miss their sum
+HZ_POS_LIMIT =(1 << 64) - 1 - 0xFFFF  # every stream position a base-taking call reaches stays below it
 
 STATUS = {
     0: "HZ_OK", -1: "HZ_EINVAL", -2: "HZ_ENOMEM", -3: "HZ_EHIP", -4: "HZ_ETOOLONG",
@@ -182,6 +184,8 @@ PROTOTYPES = [
     ("hz_block_sums_check", _I, [_P, _P, _U64, _P, _U64, _P]),
     ("hz_seekable_attach_file", _I, [ctypes.c_char_p, _U64, _U32, ctypes.POINTER(_I)]),
     ("hz_extract_stream_verified", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _I, ctypes.POINTER(_U64)]),
+    ("hz_block_sums_mark", _I, [_P, _P, _U64, _P, _U64, _P, _U32]),
+    ("hz_seekable_salvage_file", _I, [ctypes.c_char_p, ctypes.c_char_p, _U64, _U32, _P, _U64, ctypes.POINTER(_U64)]),
 ]
 
 _lib = None

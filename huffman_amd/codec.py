@@ -470,6 +470,25 @@ def extract_verified(path, out_path=None, window_bytes=256 << 20, verbose=False)
     check(rc, "hz_extract_stream_verified")
 
 
+def salvage(path, out_path=None, window_bytes=256 << 20, keep_unverified=False):
+    """Recover what a damaged seekable file (with sums) still holds: every block is decoded from the stored
+    table on its own and checked against its stored sum. Returns the list of ALL blocks that failed, ascending
+    (block b is bytes [4096 b, 4096 (b + 1)) of the original); out_path receives the original with those
+    blocks as zeros (keep_unverified=True: as whatever they decoded to) and its full size. out_path=None:
+    scan only. A completed salvage does not raise, whatever it lost (hz_seekable_salvage_file)."""
+    lib = load()
+    args = (os.fsencode(path), None if out_path is None else os.fsencode(out_path), window_bytes,
+            _lib.HZ_SALVAGE_KEEP_UNVERIFIED if keep_unverified else 0)
+    nbad = ctypes.c_uint64()
+    # room for every block (the footer alone says how many; a file the call will refuse gets one word)
+    info = _lib.SeekableInfo()
+    known = lib.hz_seekable_info_file(args[0], ctypes.byref(info)) == 0 and info.present
+    bad = np.zeros(max(info.nblocks if known else 0, 1), dtype=np.uint64)
+    check(lib.hz_seekable_salvage_file(*args, bad.ctypes.data_as(ctypes.c_void_p), bad.size, ctypes.byref(nbad)),
+          "hz_seekable_salvage_file")
+    return [int(b) for b in bad[:nbad.value]]
+
+
 class Device:
     """Stage API on device pointers (ints), stream-ordered on one HIP stream."""
 
@@ -509,6 +528,12 @@ class Device:
         """The same sums compared with the words at d_expect: the smallest block_base + i whose block differs
         is folded (atomic minimum) into the u64 at d_bad, which the caller set (hz_block_sums_check)."""
         check(self.lib.hz_block_sums_check(self.h, d_in, n, d_expect, block_base, d_bad), "hz_block_sums_check")
+
+    def block_sums_mark(self, d_data, n, d_expect, block_base, d_bits, flags=0):
+        """The same comparison with every verdict kept: bit block_base + i of the u32 bitmap at d_bits (the
+        caller's, zeroed by the caller) is set for every block that differs, and with HZ_SUMS_ZERO_BAD that
+        block's bytes below n are overwritten with zeros (hz_block_sums_mark)."""
+        check(self.lib.hz_block_sums_mark(self.h, d_data, n, d_expect, block_base, d_bits, flags), "hz_block_sums_mark")
 
     def codebook_build(self, d_hist, d_cb):
         """Device codebook: d_hist (u64 x 65536) -> d_cb (sizeof(Codebook) bytes)."""

@@ -198,6 +198,18 @@ extern "C" int hz_block_sums_check(hz_ctx* c, const uint8_t* d_in, uint64_t n, c
     return e == hipSuccess ? HZ_OK : hz_hip_fail(e, "launch_block_sums_check", __FILE_NAME__, __LINE__);
 }
 
+extern "C" int hz_block_sums_mark(hz_ctx* c, uint8_t* d_data, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                  uint32_t* d_bits, uint32_t flags) {
+    if (!c || (flags & ~HZ_SUMS_ZERO_BAD)) return HZ_EINVAL;
+    if (n == 0) return HZ_OK;
+    if (!d_data || !d_expect || !d_bits || (((uintptr_t)d_data) & 15) || (((uintptr_t)d_expect) & 3) || (((uintptr_t)d_bits) & 3))
+        return HZ_EINVAL;
+    HZ_TRY(hipSetDevice(c->device));
+    const hipError_t e = launch_block_sums_mark(d_data, n, d_expect, block_base, d_bits, (flags & HZ_SUMS_ZERO_BAD) != 0, c->ncu,
+                                                c->stream);  // (the kernel reports no errors)
+    return e == hipSuccess ? HZ_OK : hz_hip_fail(e, "launch_block_sums_mark", __FILE_NAME__, __LINE__);
+}
+
 extern "C" uint64_t hz_ranges_bytes(uint64_t n) { return range_geom(n / 2).bytes; }
 
 extern "C" int hz_hist16_ranges(hz_ctx* c, const uint8_t* d_in, uint64_t n, uint64_t* d_hist, int accumulate,

@@ -315,6 +315,10 @@ hipError_t launch_hist16_ranges(const uint8_t* d_in, uint64_t n, unsigned long l
 hipError_t launch_block_sums(const uint8_t* d_in, uint64_t n, uint32_t* d_sums, int ncu, hipStream_t s);
 hipError_t launch_block_sums_check(const uint8_t* d_in, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
                                    unsigned long long* d_bad, int ncu, hipStream_t s);
+// every block whose word differs from d_expect's: bit block_base + i of the bitmap at d_bits set (atomic OR), and
+// with zero_bad its bytes below n overwritten with zeros
+hipError_t launch_block_sums_mark(uint8_t* d_data, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                  uint32_t* d_bits, bool zero_bad, int ncu, hipStream_t s);
 // ---- hz_pack.hip (and ensure_lds_limit, launch_scan: hz_device.h) -------------
 // d_ranges (nullable): the range plan of d_in from launch_hist16_ranges; *used_ranges = 1 when the
 // pack took it (else count + scan + write)

@@ -1,7 +1,8 @@
 // hz_stream.cpp -- the file-level `archive` / `extract` flows (Compressor.cu:315-632,
-// Decompressor.cu:47-114), streamed through bounded host and device memory on the process-wide context.
+// Decompressor.cu:47-114), streamed through bounded host and device memory on the process-wide context,
+// and the flows of seekable files that walk a whole file the same way (attach, verified extract, salvage).
 // Each flow is a struct with one function per step; its file I/O is hz_file_io.cpp and its chunk and
-// window arithmetic hz_stream_plan.h, both free of HIP calls.
+// window arithmetic hz_stream_plan.h and hz_salvage_plan.h, all free of HIP calls.
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -19,12 +20,14 @@
 
 #include "hz_file_io.h"
 #include "hz_host.h"
+#include "hz_salvage_plan.h"
 #include "hz_seekable.h"
 #include "hz_stream_plan.h"
 
 using namespace hz;
 
 static_assert(kPlanBlockSyms == (uint64_t)kBlockSyms, "hz_stream_plan.h counts in the kernels' blocks");
+static_assert(kSalvageBlockSyms == (uint64_t)kBlockSyms, "hz_salvage_plan.h counts in the kernels' blocks");
 
 namespace {
 
@@ -994,6 +997,199 @@ extern "C" int hz_extract_stream_verified(const char* in_path, const char* out_p
     return timed_call([&] {
         return ExtractFlow{in_path, out_path, chunk_bytes, verbose, nullptr, ExtractFlow::kVerified, 0, bad_block}.run_verified();
     });
+}
+
+namespace {
+
+// Salvage of a damaged seekable file (hz_seekable_salvage_file): the table restarts the decode at every block
+// and the sums say which blocks came out right, so the file is walked in windows of blocks (SalvagePlan,
+// hz_salvage_plan.h: cut from a table that may itself be damaged) and every block is judged on its own.
+// A window: its payload span read and uploaded, its output zero-filled, ONE hz_decode_ranges call with one
+// range (a block that fails the decoder's checks is flagged and stores nothing: it keeps the zeros),
+// hz_block_sums_mark on the output into one device bitmap for the whole file, the output copied out, one
+// hz_ctx_sync, and the window's bytes handed to the writer beside the next window's read and device work.
+// The sync's HZ_EFORMAT / HZ_EINVAL with flagged blocks counted is the decoder's report of those blocks, not
+// a failure of the flow. Memory: one payload window and one output window on the device, one pinned payload
+// window and two pinned output windows, the table, the sums and the bitmap.
+struct SalvageFlow {
+    const char* in_path;
+    const char* out_path;
+    uint64_t chunk_bytes;
+    uint32_t flags;
+    uint64_t* bad_blocks;
+    uint64_t bad_cap;
+    uint64_t* nbad;
+
+    hz_ctx* c = nullptr;
+    bool write = false;
+    hz_seekable_info si;
+    hz_header_info info;
+    uint64_t fsize = 0, nsym = 0, nblocks = 0, pay_bytes = 0;
+    uint64_t in_cap = 0, out_cap = 0;
+    int ob = 0;  // the pinned output buffer of the window in flight
+
+    // buffers first, guards last (see StreamGuard)
+    FileReader fin{&g_timing};
+    Spans spans;
+    std::vector<uint8_t> head;
+    std::unique_ptr<hz_codebook> cb{new hz_codebook()};
+    std::vector<uint64_t> table;
+    std::vector<uint32_t> sums, bits;
+    DevBuf dwin, dout, dseek, dsums, dbits, dstats, drange;
+    PinnedBuf hin, hout[2], hrange;
+    uint64_t stats[HZ_RANGES_STATS_WORDS] = {0, 0, 0, 0};
+    FileWriter fout{&g_timing};
+    DrainGuard drain;
+
+    int open_and_parse() {
+        if (nbad) *nbad = 0;
+        if (!in_path || !nbad || (flags & ~HZ_SALVAGE_KEEP_UNVERIFIED) || (bad_cap && !bad_blocks)) return HZ_EINVAL;
+        if (chunk_bytes < HZ_SEEKABLE_MIN_WINDOW) return HZ_EINVAL;
+        write = out_path != nullptr;
+        chunk_bytes &= ~(uint64_t)15;
+        int rc = fin.open(in_path);
+        if (rc) return rc;
+        if ((rc = image_end_fd(fin.fd(), fin.size(), &fsize, &si))) return rc;
+        if (!si.present) return HZ_EFORMAT;
+        if (!(si.flags & HZ_SEEKABLE_SUMS)) return HZ_EINVAL;
+        head.resize(std::min<uint64_t>(fsize, kMaxHeaderBytes));
+        if ((rc = fin.read(head.data(), head.size(), 0))) return rc;
+        if ((rc = parse_header_for_extract(head, cb.get(), &info))) return rc;
+        if (si.n != info.n) return HZ_EFORMAT;
+        nsym = info.n / 2;
+        nblocks = si.nblocks;
+        pay_bytes = fsize > info.payload_byte ? fsize - info.payload_byte : 0;
+        // a header whose N overstates the payload must not size the output: no decode could fill it
+        if (!payload_holds(pay_bytes, info.payload_bit, nsym, cb->min_len)) return HZ_EFORMAT;
+        table.resize(hz_seek_bytes(nsym) / 8);
+        sums.resize(nblocks);
+        bits.assign((nblocks + 31) / 32, 0u);
+        if (!table.empty() && (rc = pread_all(fin.fd(), (uint8_t*)table.data(), 8 * table.size(), si.seek_off))) return rc;
+        if (!sums.empty() && (rc = pread_all(fin.fd(), (uint8_t*)sums.data(), 4 * sums.size(), si.sums_off))) return rc;
+        return HZ_OK;
+    }
+
+    int open_output() {
+        if (!write) return HZ_OK;
+        if (int rc = fout.open(out_path)) return rc;
+        fout.reserve(info.n);
+        return HZ_OK;
+    }
+
+    // The context, the decode tables, the buffers; the table and the sums uploaded once, the bitmap zeroed.
+    int prepare() {
+        int rc = timed_default_ctx(&c);
+        if (rc) return rc;
+        drain.s = c->stream;
+        const auto tu = Clock::now();
+        if ((rc = hz_codebook_upload_decode(c, cb.get()))) return rc;
+        g_timing.host_ms += ms_since(tu);
+        // no window larger than the file needs, so a small file takes small buffers
+        in_cap = std::min(chunk_bytes, std::max<uint64_t>((pay_bytes + 15) & ~(uint64_t)15, 16));
+        out_cap = std::min(std::max<uint64_t>(chunk_bytes / HZ_SUM_BLOCK_BYTES, 1), nblocks) * HZ_SUM_BLOCK_BYTES;
+        const auto ta = Clock::now();
+        if ((rc = dwin.alloc(in_cap + 16)) || (rc = dout.alloc(out_cap)) || (rc = dseek.alloc(8 * table.size())) ||
+            (rc = dsums.alloc(4 * sums.size())) || (rc = dbits.alloc(4 * bits.size())) ||
+            (rc = dstats.alloc(8 * HZ_RANGES_STATS_WORDS)) || (rc = drange.alloc(sizeof(hz_range))))
+            return rc;
+        if ((rc = hin.alloc(in_cap)) || (rc = hrange.alloc(sizeof(hz_range)))) return rc;
+        for (int i = 0; i < 2; ++i)
+            if (write && (rc = hout[i].alloc(out_cap))) return rc;
+        g_timing.alloc_ms += ms_since(ta);
+        HZ_TRY(hipMemsetAsync(dbits.p, 0, 4 * bits.size(), c->stream));
+        if ((rc = spans.copy(c->stream, &g_timing.h2d_ms, dseek.p, table.data(), 8 * table.size(), hipMemcpyHostToDevice)) ||
+            (rc = spans.copy(c->stream, &g_timing.h2d_ms, dsums.p, sums.data(), 4 * sums.size(), hipMemcpyHostToDevice)))
+            return rc;
+        return HZ_OK;
+    }
+
+    int window(const SalvageWindow& w) {
+        int rc;
+        const uint64_t begin = std::min(w.byte_begin, pay_bytes), len = std::min(w.byte_end, pay_bytes) - begin;
+        const uint64_t sym0 = w.first_block * kBlockSyms, syms = std::min(nsym - sym0, w.nblocks * kBlockSyms);
+        if (len > in_cap || 2 * syms > out_cap) return HZ_EFORMAT;  // (the plan keeps both within chunk_bytes)
+        if (len) {
+            if ((rc = fin.read(hin.p, len, info.payload_byte + begin))) return rc;
+            if ((rc = spans.copy(c->stream, &g_timing.h2d_ms, dwin.p, hin.p, len, hipMemcpyHostToDevice))) return rc;
+        }
+        // (the wait of the window before this one is behind us: its copy of the range has been made)
+        *reinterpret_cast<hz_range*>(hrange.p) = hz_range{sym0, syms, 0};
+        HZ_TRY(hipMemcpyAsync(drange.p, hrange.p, sizeof(hz_range), hipMemcpyHostToDevice, c->stream));
+        HZ_TRY(hipMemsetAsync(dout.p, 0, 2 * syms, c->stream));
+        rc = spans.timed(c->stream, &g_timing.kernel_ms, [&]() -> int {
+            if (int r2 = hz_decode_ranges(c, (const uint8_t*)dwin.p, len, begin, (const uint64_t*)dseek.p, nsym,
+                                          (const hz_range*)drange.p, 1, (uint8_t*)dout.p, 2 * syms, (uint64_t*)dstats.p, 0))
+                return r2;
+            HZ_TRY(hipMemcpyAsync(stats, dstats.p, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
+            return hz_block_sums_mark(c, (uint8_t*)dout.p, 2 * syms, (const uint32_t*)dsums.p + w.first_block, w.first_block,
+                                      (uint32_t*)dbits.p, (flags & HZ_SALVAGE_KEEP_UNVERIFIED) ? 0u : HZ_SUMS_ZERO_BAD);
+        });
+        if (rc) return rc;
+        if (write && (rc = spans.copy(c->stream, &g_timing.d2h_ms, hout[ob].p, dout.p, 2 * syms, hipMemcpyDeviceToHost))) return rc;
+        rc = hz_ctx_sync(c);  // the window's one host wait
+        spans.fold();
+        // flagged blocks are what a salvage expects to meet: they stored nothing and their sums judge them
+        if (rc && !((rc == HZ_EFORMAT || rc == HZ_EINVAL) && stats[3] > 0)) return rc;
+        if (write) {
+            if ((rc = fout.wait())) return rc;  // the previous window's write: the other buffer is free again
+            fout.start(hout[ob].p, 2 * syms, (uint64_t)HZ_SUM_BLOCK_BYTES * w.first_block);
+            ob ^= 1;
+        }
+        return HZ_OK;
+    }
+
+    // The bitmap home, its set bits counted and listed in ascending order.
+    int report() {
+        int rc;
+        if (!bits.empty()) {
+            rc = spans.copy(c->stream, &g_timing.d2h_ms, bits.data(), dbits.p, 4 * bits.size(), hipMemcpyDeviceToHost);
+            if (rc || (rc = hz_ctx_sync(c))) return rc;
+            spans.fold();
+        }
+        uint64_t count = 0;
+        for (uint64_t b = 0; b < nblocks; ++b) {
+            if (!(bits[b >> 5] >> (b & 31) & 1u)) continue;
+            if (count < bad_cap) bad_blocks[count] = b;
+            ++count;
+        }
+        *nbad = count;
+        return HZ_OK;
+    }
+
+    // Whatever ends the flow early, the output ends at its last written window, never at its reserved size.
+    int run() {
+        const int rc = windows();
+        if (rc) {
+            (void)fout.wait();
+            (void)fout.close();
+        }
+        return rc;
+    }
+
+    int windows() {
+        int rc;
+        if ((rc = open_and_parse()) || (rc = open_output())) return rc;
+        if (nblocks) {
+            if ((rc = prepare())) return rc;
+            SalvagePlan plan(table.data(), nblocks, pay_bytes, cb->max_len, chunk_bytes);
+            SalvageWindow w;
+            while (plan.next(&w))
+                if ((rc = window(w))) return rc;
+            if ((rc = fout.wait()) || (rc = report())) return rc;
+        }
+        if (write && info.is_odd) {
+            const uint8_t b = (uint8_t)info.last_byte;
+            if ((rc = fout.write_now(&b, 1, 2 * nsym))) return rc;
+        }
+        return write ? fout.close() : HZ_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int hz_seekable_salvage_file(const char* in_path, const char* out_path, uint64_t chunk_bytes, uint32_t flags,
+                                        uint64_t* bad_blocks, uint64_t bad_cap, uint64_t* nbad) {
+    return timed_call([&] { return SalvageFlow{in_path, out_path, chunk_bytes, flags, bad_blocks, bad_cap, nbad}.run(); });
 }
 
 extern "C" int hz_archive_stream_seek(const char* in_path, const char* out_path, uint64_t chunk_bytes, int verbose,

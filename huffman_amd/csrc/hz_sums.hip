@@ -2,6 +2,7 @@
 //
 //   k_block_sums        one Adler-32 (RFC 1950) per 4096 bytes, the last block zero-extended
 //   k_block_sums_check  the same words compared with expected ones: the smallest block that differs
+//   k_block_sums_mark   the same comparison with every block that differs marked in a bitmap, and zeroed on request
 //
 // The reference has no counterpart: its format carries no checksum.
 #include "hz_device.h"
@@ -92,6 +93,47 @@ __global__ __launch_bounds__(kSumThreads) void k_block_sums_check(const uint8_t*
     }
 }
 
+// Zeros over block b's bytes below n: the layout of sums_block's loads, a 16-byte store wherever the whole
+// vector lies below n. The vector that holds byte n - 1 goes out as its whole words below n and then single
+// bytes, so no store touches a byte at or past n.
+HZ_DEV void sums_zero_block(uint8_t* data, uint64_t n, uint64_t b, uint32_t lane) {
+    const uint64_t base = b * kSumBlockBytes;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint64_t a = base + 16u * lane + 1024u * j;
+        if (a + 16 <= n) {
+            *reinterpret_cast<uint4*>(data + a) = make_uint4(0u, 0u, 0u, 0u);
+        } else if (a < n) {
+            for (uint64_t q = a; q < n;) {
+                if (q + 4 <= n) {
+                    *reinterpret_cast<uint32_t*>(data + q) = 0u;
+                    q += 4;
+                } else {
+                    data[q++] = 0;
+                }
+            }
+        }
+    }
+}
+
+// The comparison again, every verdict kept: a block whose word differs sets bit (block_base + b) & 31 of
+// bits[(block_base + b) >> 5] (the caller's bitmap, never initialised here: the windows of one file fold into
+// one) and, with `zero`, loses its bytes below n. The word and expect[b] are the same in every lane: the
+// branch is wave-uniform, and a block that matches is never written.
+__global__ __launch_bounds__(kSumThreads) void k_block_sums_mark(uint8_t* data, uint64_t n, uint64_t nblocks,
+                                                                const uint32_t* __restrict__ expect, uint64_t block_base,
+                                                                uint32_t* bits, bool zero) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t step = (uint64_t)gridDim.x * (kSumThreads / kWave);
+    for (uint64_t b = (uint64_t)blockIdx.x * (kSumThreads / kWave) + wave_id(); b < nblocks; b += step) {
+        const uint32_t word = sums_block(data, n, b, lane);
+        if (word == expect[b]) continue;
+        const uint64_t g = block_base + b;
+        if (lane == 0u) atomicOr(bits + (g >> 5), 1u << (uint32_t)(g & 31u));
+        if (zero) sums_zero_block(data, n, b, lane);
+    }
+}
+
 // eight workgroups (32 waves, 128 KiB of loads in flight) per CU, the rest by the grid stride
 static unsigned sums_grid(uint64_t nblocks, int ncu) { return (unsigned)grid_clamp((nblocks + 3) / 4, (uint64_t)ncu * 8); }
 
@@ -108,6 +150,15 @@ hipError_t launch_block_sums_check(const uint8_t* d_in, uint64_t n, const uint32
     const uint64_t nblocks = (n + kSumBlockBytes - 1) / kSumBlockBytes;
     hipLaunchKernelGGL(k_block_sums_check, dim3(sums_grid(nblocks, ncu)), dim3(kSumThreads), 0, s, d_in, n, nblocks, d_expect,
                        block_base, d_bad);
+    return hipGetLastError();
+}
+
+hipError_t launch_block_sums_mark(uint8_t* d_data, uint64_t n, const uint32_t* d_expect, uint64_t block_base,
+                                  uint32_t* d_bits, bool zero_bad, int ncu, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t nblocks = (n + kSumBlockBytes - 1) / kSumBlockBytes;
+    hipLaunchKernelGGL(k_block_sums_mark, dim3(sums_grid(nblocks, ncu)), dim3(kSumThreads), 0, s, d_data, n, nblocks, d_expect,
+                       block_base, d_bits, zero_bad);
     return hipGetLastError();
 }
 

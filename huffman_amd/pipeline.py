@@ -102,6 +102,17 @@ class StreamCodec:
         assert expect.numel() * 4 >= block_sums_bytes(x.numel()) and expect.element_size() == 4
         self.dev.block_sums_check(x.data_ptr(), x.numel(), expect.data_ptr(), block_base, bad.data_ptr())
 
+    def block_sums_mark(self, x, expect, bits, block_base=0, zero_bad=False):
+        """Compare the block checksums of a uint8 device tensor (16-byte aligned) with `expect` (int32, one
+        word per block): bit block_base + i of the bitmap `bits` (int32 words, the caller's: zero it first,
+        calls accumulate) is set for every block that differs. zero_bad=True also overwrites those blocks'
+        bytes of x with zeros; a matching block is never written (hz_block_sums_mark)."""
+        nblocks = block_sums_bytes(x.numel()) // 4
+        assert expect.numel() >= nblocks and expect.element_size() == 4 and bits.element_size() == 4
+        assert bits.numel() * 32 >= block_base + nblocks
+        self.dev.block_sums_mark(x.data_ptr(), x.numel(), expect.data_ptr(), block_base, bits.data_ptr(),
+                                 _lib.HZ_SUMS_ZERO_BAD if zero_bad else 0)
+
     def histogram(self, x, accumulate=False):
         n = x.numel()
         # the range plan needs a 16-byte aligned input (hz_hist16_ranges); offset views take hz_hist16

@@ -129,6 +129,24 @@ int hz_block_sums(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, uint32_t *d_sums
 int hz_block_sums_check(hz_ctx *ctx, const uint8_t *d_in, uint64_t n, const uint32_t *d_expect,
                         uint64_t block_base, uint64_t *d_bad);
 
+/* The comparison with EVERY verdict kept, and the damaged blocks blanked on request: block i's word is
+ * compared with d_expect[i] as above, and a block that differs does a 32-bit atomic OR of bit
+ * (block_base + i) & 31 into d_bits[(block_base + i) >> 5] (4-byte aligned; the caller sizes it for the
+ * largest block_base + i it will pass). The bitmap is the caller's: the call never initialises it, so
+ * several calls (the windows of hz_seekable_salvage_file, each at its block_base) fold into one bitmap;
+ * zero it first, and afterwards its set bits are exactly the failing blocks. With flags =
+ * HZ_SUMS_ZERO_BAD a block that differs also has its bytes [4096 i, min(4096 (i + 1), n)) of d_data
+ * overwritten with zeros by the wave that summed it (a wave-uniform branch): 16-byte stores wherever the
+ * whole vector lies below n, and the vector that holds byte n - 1 as whole words and then single bytes,
+ * so no store touches a byte at or past n. A block that matches is never written, and without the flag
+ * nothing of d_data is. Loads, alignment of d_data, grid shape, stream order and capturability are
+ * hz_block_sums' (one per-block body in hz_sums.hip). No scratch, and the context's error word is not
+ * touched. n == 0: HZ_OK, nothing launched. HZ_EINVAL: a null pointer, d_data not 16-byte aligned,
+ * d_expect or d_bits not 4-byte aligned, a flag other than HZ_SUMS_ZERO_BAD. */
+#define HZ_SUMS_ZERO_BAD 1u
+int hz_block_sums_mark(hz_ctx *ctx, uint8_t *d_data, uint64_t n, const uint32_t *d_expect,
+                       uint64_t block_base, uint32_t *d_bits, uint32_t flags);
+
 /* Host codebook from a host histogram with the reference's semantics: thrust
  * stable sort (Compressor.cu:378-393,414,419-425) + GenerateCL / GenerateCW /
  * toCpu (gpuHuffmanConstruction.h:353-494,551-579). U == 1 gets code "0"
@@ -913,6 +931,49 @@ int hz_seekable_verify_file(const char *path, uint64_t *bad_block);
 int hz_seekable_attach_file(const char *path, uint64_t chunk_bytes, uint32_t flags, int *attached);
 int hz_extract_stream_verified(const char *in_path, const char *out_path, uint64_t chunk_bytes, int verbose,
                                uint64_t *bad_block);
+
+/* Salvage of a damaged seekable file: EVERY bad block named, the rest kept. The readers above stop at the
+ * first problem; one flipped payload bit damages one block, and the file carries what recovery needs: the
+ * table restarts the decode at every block independently of the block before it, and the sums say which
+ * blocks came out right. hz_seekable_salvage_file writes to out_path the original with every block that
+ * could not be verified replaced by 4096 zero bytes (its share of n for the last block), and lists those
+ * blocks: *nbad their number, bad_blocks[0 .. min(*nbad, bad_cap)) the blocks in ascending order
+ * (bad_blocks may be NULL with bad_cap 0). The output's size is exactly n, the odd last byte from the
+ * header included. A COMPLETED SALVAGE RETURNS HZ_OK whether or not blocks were lost. out_path NULL:
+ * decode and check, write nothing -- the whole-file scan that names every bad block.
+ *
+ * Refusals: a plain file HZ_EFORMAT; a trailer without sums HZ_EINVAL; a header N that differs from the
+ * footer's HZ_EFORMAT; chunk_bytes below HZ_SEEKABLE_MIN_WINDOW, a NULL in_path or nbad, an unknown flag
+ * HZ_EINVAL; a missing file HZ_ENOENT before any device call; a header that does not parse: its status,
+ * nothing written. A DAMAGED CODEBOOK OR FOOTER IS NOT SALVAGEABLE: without the codebook no block decodes,
+ * and without the footer the file is a plain file.
+ *
+ * The stored table and sums are read from the trailer and uploaded once, and a device bitmap of
+ * ceil(nblocks / 32) words is zeroed. The blocks are cut into WINDOWS from the stored table, WHICH MAY
+ * ITSELF BE DAMAGED (hz_salvage_plan.h): a block is trusted when its own two entries ascend, lie at most
+ * 2048 x max_len bits apart and end inside the payload -- the decoder's own check, so a block that is not
+ * trusted is flagged whatever it is given -- and a window's payload span is the hull of hz_seek_span of its
+ * trusted blocks; a block joins the window while that span and the window's output (4096 bytes a block)
+ * stay within chunk_bytes. Per window: its span is read and uploaded, its device output zero-filled, ONE
+ * hz_decode_ranges call with one range decodes it (a block the decoder flags stores nothing and keeps
+ * the zeros), hz_block_sums_mark judges every block of the output at block_base = the window's first
+ * block (with HZ_SUMS_ZERO_BAD unless HZ_SALVAGE_KEEP_UNVERIFIED is set), the output is copied out, and
+ * one hz_ctx_sync -- the window's only host wait -- brings the decoder's status home: HZ_EFORMAT or
+ * HZ_EINVAL with flagged blocks counted (d_stats[3] > 0) is the expected report and the flow goes on, any
+ * other status ends it. The window's bytes go to file offset 4096 x first block beside the next window's
+ * work. Host and device memory are bounded by chunk_bytes, the table, the sums and the bitmap, whatever
+ * the file's size. Whatever ends the flow early, the output ends at its last written byte.
+ *
+ * WHAT A VERDICT MEANS. A block is reported bad when its output does not match its stored sum. The cause
+ * may be damage to its payload bits, a damaged table entry (which can cost the two blocks that share it) or
+ * a damaged sum word; in the last case the decoded bytes were right, and HZ_SALVAGE_KEEP_UNVERIFIED keeps
+ * every block's decoded bytes in the output (a flagged block's are still zeros: it decoded to nothing), so
+ * the caller can judge them by other means. A block the decoder flagged whose stored sum is that of 4096
+ * zero bytes is reported good: its output is zeros and matches, the same strength of evidence every other
+ * block has. */
+#define HZ_SALVAGE_KEEP_UNVERIFIED 1u
+int hz_seekable_salvage_file(const char *in_path, const char *out_path, uint64_t chunk_bytes, uint32_t flags,
+                             uint64_t *bad_blocks, uint64_t bad_cap, uint64_t *nbad);
 
 #ifdef __cplusplus
 }
